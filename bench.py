@@ -13,9 +13,18 @@ rel_tol 1e-4, d0+dd = 128+64 samples, matrix A already resident in HBM when the 
 Prints ONE JSON line (rank 0).  `value` = algorithmic GFLOP/s of compress+factor+solve (flop model of
 SURVEY.md section 8(d): 4 N^2 d for the sketch + the per-node terms) over the max-over-ranks step
 time.  `roofline` describes the dominant kernel (the sketch DGEMM, FP64 MFMA bound) with the launch
-duration measured by HIP events on the launch stream; `cpu_baseline` is the reference's own CPU HSS
-(oracle/_ref, built from /root/reference by oracle/ref/Makefile) timed on this host on a bounded
-sample (N = 32768 = BASELINE configs[1], same options) -- the only place anything under oracle/ is used here.
+duration measured by HIP events on the launch stream.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the line.  --full adds,
+on the headline workload, what takes work of its own: the correctness checks (`checks`), the apply / solve sweeps
+(`sweeps`), the sketch's HBM traffic from counter passes (`roofline.traffic`), with N > 1 the synchronised diagnostic
+step (`comm_s`), and `cpu_baseline` -- the reference's own CPU HSS (oracle/_ref, built by oracle/ref/Makefile from
+the reference's sources) timed on this host on a bounded sample (N = 32768 = BASELINE configs[1], same options), the
+only place anything under oracle/ is used here.  The secondary workloads (--workload kernel / host / blr_front) always
+report their full lines.
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float64, at most 64 MB in
+all); the inputs are fixed by the arguments, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -28,6 +37,26 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_FP64_MFMA_TFLOPS = 78.6  # gfx950 FP64 matrix peak (MI355X spec; 256 CU x 4 SIMD x 32 flop/clk x 2.4 GHz)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one out_dir/<name>.npy per array, as float64.  An array larger than its share of DUMP_LIMIT_BYTES is
+    replaced by a fixed sample of its rows (seed 0, ascending), whose indices are written as <name>_rows.npy."""
+    import numpy as np
+    if not out_dir:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1) - 1024     # (less the .npy headers)
+    for name, v in arrays.items():
+        v = np.asarray(v, dtype=np.float64)
+        if v.nbytes > share:
+            row_bytes = v.nbytes // v.shape[0]
+            k = max(1, share // (row_bytes + 8))
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], k, replace=False))
+            v = v[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def parse():
@@ -39,7 +68,12 @@ def parse():
     p.add_argument("--leaf", type=int, default=256)
     p.add_argument("--rel-tol", type=float, default=1e-4)
     p.add_argument("--nrhs", type=int, default=1)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="headline workload: also run the checks, the apply / solve sweeps, the counter passes and the CPU baseline "
+                        "(a plain run times the steps and prints the line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the timed path computed in its last step as DIR/<name>.npy (float64, at most 64 MB in all)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (of --full, and of --workload blr_front)")
     p.add_argument("--factor-ahead", action=argparse.BooleanOptionalAction, default=None,
                    help="toeplitz workload: tell the library that a factorization follows -- it enqueues every tree level's ULV factorization "
                    "on a second stream as soon as the compression has settled the level (SPXHSSOptions::factor_ahead).  Default: on for "
@@ -116,6 +150,8 @@ def kernel_workload(a, torch, dist, world, rank, local):
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0:
+        dump_outputs(a.dump_outputs, {"w": w, "perm": perm})   # (regression weights in the clustered order, and that order)
     st = H.stats()
     resid = float(np.linalg.norm(H.mult(w) - y[perm - 1]) / np.linalg.norm(y))
     out = {"metric": "hss_kernel_fit_points_per_s", "value": n / (elapsed / a.steps), "unit": "points/s", "n_gpus": world,
@@ -202,6 +238,7 @@ def host_workload(a, L, hk):
             H.destroy()
         H, x = step()
     elapsed = (time.perf_counter() - t0) / a.steps
+    dump_outputs(a.dump_outputs, {"x": x})
     st = H.stats()
     f_total = st["f_sketch"] + st["f_local"] + st["f_reduce"] + st["f_id"] + st["f_ortho"] + st["f_ulv"] + st["f_solve"]
     resid = float(np.linalg.norm(H.mult(x) - b) / np.linalg.norm(b))
@@ -294,6 +331,7 @@ def blr_front_workload(a, L, hk, torch):
         sts.append(F.stats())
     torch.cuda.synchronize()
     elapsed = (time.perf_counter() - t0) / a.steps
+    dump_outputs(a.dump_outputs, {"x": x})
     st = sts[-1]
     med = lambda k: sorted(s_[k] for s_ in sts)[len(sts) // 2]
     # phases on the device clock: extra steps OUTSIDE the timed region with the stopwatches on (one stream then: the timed
@@ -431,6 +469,7 @@ def blr_front_device_workload(a, L, hk, torch, BF, nx, ny, leaf):
         sts.append(F.stats())
     torch.cuda.synchronize()
     elapsed = (time.perf_counter() - t0) / a.steps
+    dump_outputs(a.dump_outputs, {"x": x})
     st = sts[-1]
     walls_out = {k_: [round(v_, 2) for v_ in vs[-a.steps:]] for k_, vs in walls.items()}   # the timed steps, call by call (host clock)
     med = lambda k: sorted(s_[k] for s_ in sts)[len(sts) // 2]
@@ -559,7 +598,7 @@ def cpu_baseline(n_small, leaf, rel_tol, n_full=100000):
     except Exception as e:  # reference library unavailable on this host: time the numpy/LAPACK port instead
         import numpy as np
         from oracle import hss_oracle as O
-        n = min(n, 8192)
+        n = min(n_small, 8192)
         A = O.toeplitz(n)
         t0 = time.time()
         H = O.HSSMatrix(A, O.Options(rel_tol=rel_tol, abs_tol=1e-8, leaf_size=leaf), rgen=type(
@@ -812,72 +851,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed / a.steps * 1e3
-
-    # ---- correctness gates reported with the number
-    import numpy as np
-    Xh = dX.get()
-    Bh = dB.get()
-    HX = H.mult(Xh)
-    resid = float(np.linalg.norm(HX - Bh) / np.linalg.norm(Bh))
-    rng = np.random.default_rng(0)
-    nc = 64  # compression error sampled on 64 random columns
-    cols = rng.integers(0, n, nc)
-    E = np.zeros((n, nc))
-    E[cols, np.arange(nc)] = 1.0
-    i = np.arange(n)
-    Ac = 1.0 / (1.0 + np.abs(i[:, None] - cols[None, :]))
-    comp_err = float(np.linalg.norm(H.mult(E) - Ac) / np.linalg.norm(Ac))
-    ax_resid = float(np.linalg.norm(Ac.T @ Xh[:, 0] - Bh[cols, 0]) / np.linalg.norm(Bh[cols, 0]))
-
-    # ---- apply / solve sweeps on their own (HBM-bound: every D, E, B resp. ULV block is read once per call)
-    reps = 10
-    dY = hk.empty((n, a.nrhs))
-
-    def timed(fn):
-        ts = []
-        for _ in range(reps):
-            barrier()
-            t1 = time.perf_counter()
-            fn()
-            barrier()
-            ts.append((time.perf_counter() - t1) * 1e3)
-        if os.environ.get("STRUMPACK_AMD_BENCH_DEBUG"):
-            print(ts, file=sys.stderr)
-        return sorted(ts)[len(ts) // 2]
-
-    # the same calls on the DEVICE clock: HIP events on the engine's stream around the launches of one call (hssk_watch_*), i.e.
-    # without the host's launch and synchronisation latencies that the wall-clock figure of a 0.1 ms call carries
-    mctx = L.SPX_d_struct_hssk_ctx(H.h)
-    hk.lib.hssk_watch_read_ms.restype = C.c_double
-    hk.lib.hssk_watch_read_ms.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-
-    def timed_device(fn):
-        if dry or not mctx:
-            return None
-        vals = []
-        for _ in range(reps):
-            barrier()
-            if hk.lib.hssk_watch_start(C.c_void_p(mctx), 6):
-                return None
-            fn()
-            hk.lib.hssk_watch_stop(C.c_void_p(mctx), 6)
-            ms = hk.lib.hssk_watch_read_ms(C.c_void_p(mctx), 6, None)
-            if ms <= 0:
-                return None
-            vals.append(ms)
-        return sorted(vals)[len(vals) // 2]
-
-    apply_ms = timed(lambda: H.mult_device(dB.ptr, dY.ptr, a.nrhs))
-    apply_dev_ms = timed_device(lambda: H.mult_device(dB.ptr, dY.ptr, a.nrhs))
-
-    def one_solve():
-        H.solve_device(dY.ptr, a.nrhs)
-    hk.check(hk.lib.hssk_memcpy_d2d(hk.ctx, dY.ptr, dB.ptr, 8 * n * a.nrhs))
-    solve_ms = timed(one_solve)
-    solve_dev_ms = timed_device(one_solve)
+    if rank == 0:
+        dump_outputs(a.dump_outputs, {"x": dX.get()})   # the solution of the last timed step (n x nrhs)
 
     st = stats[-1]
-    st2 = H.stats()
     f_total = st["f_sketch"] + st["f_local"] + st["f_reduce"] + st["f_id"] + st["f_ortho"] + st["f_ulv"] + st["f_solve"]
     value = f_total / (ms_per_step * 1e-3) * 1e-9
     # dominant kernel: the sketch DGEMM.  Algorithmic flops per launch = 2 d N^2 (4 N^2 d
@@ -889,21 +866,6 @@ def main():
     # workgroup slots; the short tail / edge launches are separate kernels outside the event bracket)
     flops_per_launch = st["sketch_kernel_flops"] / launches
     ach = flops_per_launch / (avg_ms * 1e-3) * 1e-12 if avg_ms > 0 else 0.0
-    # HBM bytes of the dominant kernel's launches, from counter passes of this very command (None without rocprofv3)
-    traffic = tsrc = None
-    if rank == 0 and world == 1 and a.sketch == "gaussian" and not os.environ.get("STRUMPACK_AMD_BENCH_INNER"):
-        extra = ["--size", str(n), "--leaf", str(a.leaf), "--rel-tol", str(a.rel_tol), "--nrhs", str(a.nrhs), "--operand", a.operand]
-        if a.factor_ahead:
-            extra.append("--factor-ahead")
-        if a.symmetric:
-            extra.append("--symmetric")
-        # the MAIN launches of both sketch products: sketch_kernel<rows / 64, transposed?, group 0>
-        tmain = measure_traffic(extra, r"sketch_kernel<\d, (true|false), 0, (true|false)>")
-        if tmain is not None:
-            traffic = tmain["bytes"]
-            tsrc = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE passes of this command (one step each), main launches of "
-                    "sketch_kernel<3, ., 0>: read %.1f GB (FETCH_SIZE x 2, the guide's gfx950 correction) + written %.2f GB per launch"
-                    % (tmain["read_bytes"] * 1e-9, tmain["write_bytes"] * 1e-9))
     out = {
         "metric": "hss_compress_ulv_factor_solve_gflops", "value": value, "unit": "GFLOP/s", "n_gpus": world,
         "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
@@ -930,21 +892,10 @@ def main():
         "flops": {"sketch": st["f_sketch"], "local": st["f_local"], "reduce": st["f_reduce"], "id": st["f_id"],
                   "ortho": st["f_ortho"], "ulv": st["f_ulv"], "solve": st["f_solve"]},
         "hss": {"rank": H.rank(), "levels": H.levels(), "memory_MB": H.memory() / 1e6, "rounds": int(st["rounds"]), "d": d},
-        "checks": {"solve_resid_H": resid, "compress_err_sampled": comp_err, "Ax_minus_b_sampled": ax_resid},
-        # bytes = the blocks each sweep reads, once (engine-side count: D, X, B for the mat-vec; X, R~, WQ, Vt0, B, Q~ for
-        # the solve) + the vectors in and out
-        # ms / GBps: wall clock of the call between two host synchronisations (what a caller sees); device_ms / device_GBps: the
-        # launches of the call on the device clock (what the kernels do)
-        "sweeps": {"apply": {"ms": apply_ms, "bytes": st2["b_mult"] + 16.0 * n * a.nrhs,
-                             "GBps": (st2["b_mult"] + 16.0 * n * a.nrhs) / (apply_ms * 1e-3) * 1e-9, "bound": "hbm (8000 GB/s); one launch, %d dependent levels" % H.levels(),
-                             "device_ms": apply_dev_ms, "device_GBps": ((st2["b_mult"] + 16.0 * n * a.nrhs) / (apply_dev_ms * 1e-3) * 1e-9) if apply_dev_ms else None},
-                   "solve": {"ms": solve_ms, "bytes": st2["b_solve"] + 16.0 * n * a.nrhs,
-                             "GBps": (st2["b_solve"] + 16.0 * n * a.nrhs) / (solve_ms * 1e-3) * 1e-9, "bound": "hbm (8000 GB/s); two launches",
-                             "device_ms": solve_dev_ms, "device_GBps": ((st2["b_solve"] + 16.0 * n * a.nrhs) / (solve_dev_ms * 1e-3) * 1e-9) if solve_dev_ms else None}},
         "roofline": {"kernel": "sketch_kernel<3> (sketch S^T = R^T op(A): 192 x 128 tiles on 8 waves, operands by LDS DMA, v_mfma_f64_16x16x4_f64)", "bound": "mfma",
                      "achieved": ach, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_FP64_MFMA_TFLOPS,
-                     "traffic": traffic,
-                     "traffic_source": tsrc, "algorithmic_bytes_per_launch": ((16.0 * d * n if generated else 8.0 * st["sketch_kernel_flops"] / launches / (2.0 * d) + 8.0 * d * n) if d else None),
+                     "traffic": None,
+                     "traffic_source": None, "algorithmic_bytes_per_launch": ((16.0 * d * n if generated else 8.0 * st["sketch_kernel_flops"] / launches / (2.0 * d) + 8.0 * d * n) if d else None),
                      "avg_launch_ms": avg_ms, "launches_per_step": launches, "flops_per_launch": flops_per_launch},
     }
     if dry:
@@ -964,17 +915,111 @@ def main():
         tfs = os.path.join(ROOT, "profiles", "r02_pmc_sjlt_traffic.json")
         if os.path.exists(tfs) and n == 100000 and world == 1:
             out["roofline"]["traffic"] = json.load(open(tfs)).get("hbm_read_bytes_per_launch")
-    if world > 1:
-        # diagnostic step with synchronised collectives: host-visible time of the compression's collectives
-        os.environ["STRUMPACK_AMD_TIME_COMM"] = "1"
-        H.destroy()
-        H = step()
-        out["comm_s"] = {"compress_collectives_synchronised": H.stats()["t_comm"], "note": "one extra step outside the timed region, every collective bracketed by stream synchronisations"}
-        del os.environ["STRUMPACK_AMD_TIME_COMM"]
+    # ---- --full: what takes work of its own beyond the timed steps
+    if a.full:
+        # ---- correctness gates reported with the number
+        import numpy as np
+        Xh = dX.get()
+        Bh = dB.get()
+        HX = H.mult(Xh)
+        resid = float(np.linalg.norm(HX - Bh) / np.linalg.norm(Bh))
+        rng = np.random.default_rng(0)
+        nc = 64  # compression error sampled on 64 random columns
+        cols = rng.integers(0, n, nc)
+        E = np.zeros((n, nc))
+        E[cols, np.arange(nc)] = 1.0
+        i = np.arange(n)
+        Ac = 1.0 / (1.0 + np.abs(i[:, None] - cols[None, :]))
+        comp_err = float(np.linalg.norm(H.mult(E) - Ac) / np.linalg.norm(Ac))
+        ax_resid = float(np.linalg.norm(Ac.T @ Xh[:, 0] - Bh[cols, 0]) / np.linalg.norm(Bh[cols, 0]))
+
+        # ---- apply / solve sweeps on their own (HBM-bound: every D, E, B resp. ULV block is read once per call)
+        reps = 10
+        dY = hk.empty((n, a.nrhs))
+
+        def timed(fn):
+            ts = []
+            for _ in range(reps):
+                barrier()
+                t1 = time.perf_counter()
+                fn()
+                barrier()
+                ts.append((time.perf_counter() - t1) * 1e3)
+            if os.environ.get("STRUMPACK_AMD_BENCH_DEBUG"):
+                print(ts, file=sys.stderr)
+            return sorted(ts)[len(ts) // 2]
+
+        # the same calls on the DEVICE clock: HIP events on the engine's stream around the launches of one call (hssk_watch_*), i.e.
+        # without the host's launch and synchronisation latencies that the wall-clock figure of a 0.1 ms call carries
+        mctx = L.SPX_d_struct_hssk_ctx(H.h)
+        hk.lib.hssk_watch_read_ms.restype = C.c_double
+        hk.lib.hssk_watch_read_ms.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+
+        def timed_device(fn):
+            if dry or not mctx:
+                return None
+            vals = []
+            for _ in range(reps):
+                barrier()
+                if hk.lib.hssk_watch_start(C.c_void_p(mctx), 6):
+                    return None
+                fn()
+                hk.lib.hssk_watch_stop(C.c_void_p(mctx), 6)
+                ms = hk.lib.hssk_watch_read_ms(C.c_void_p(mctx), 6, None)
+                if ms <= 0:
+                    return None
+                vals.append(ms)
+            return sorted(vals)[len(vals) // 2]
+
+        apply_ms = timed(lambda: H.mult_device(dB.ptr, dY.ptr, a.nrhs))
+        apply_dev_ms = timed_device(lambda: H.mult_device(dB.ptr, dY.ptr, a.nrhs))
+
+        def one_solve():
+            H.solve_device(dY.ptr, a.nrhs)
+        hk.check(hk.lib.hssk_memcpy_d2d(hk.ctx, dY.ptr, dB.ptr, 8 * n * a.nrhs))
+        solve_ms = timed(one_solve)
+        solve_dev_ms = timed_device(one_solve)
+
+        st2 = H.stats()
+        out["checks"] = {"solve_resid_H": resid, "compress_err_sampled": comp_err, "Ax_minus_b_sampled": ax_resid}
+        # bytes = the blocks each sweep reads, once (engine-side count: D, X, B for the mat-vec; X, R~, WQ, Vt0, B, Q~ for
+        # the solve) + the vectors in and out
+        # ms / GBps: wall clock of the call between two host synchronisations (what a caller sees); device_ms / device_GBps: the
+        # launches of the call on the device clock (what the kernels do)
+        out["sweeps"] = {"apply": {"ms": apply_ms, "bytes": st2["b_mult"] + 16.0 * n * a.nrhs,
+                                   "GBps": (st2["b_mult"] + 16.0 * n * a.nrhs) / (apply_ms * 1e-3) * 1e-9, "bound": "hbm (8000 GB/s); one launch, %d dependent levels" % H.levels(),
+                                   "device_ms": apply_dev_ms, "device_GBps": ((st2["b_mult"] + 16.0 * n * a.nrhs) / (apply_dev_ms * 1e-3) * 1e-9) if apply_dev_ms else None},
+                         "solve": {"ms": solve_ms, "bytes": st2["b_solve"] + 16.0 * n * a.nrhs,
+                                   "GBps": (st2["b_solve"] + 16.0 * n * a.nrhs) / (solve_ms * 1e-3) * 1e-9, "bound": "hbm (8000 GB/s); two launches",
+                                   "device_ms": solve_dev_ms, "device_GBps": ((st2["b_solve"] + 16.0 * n * a.nrhs) / (solve_dev_ms * 1e-3) * 1e-9) if solve_dev_ms else None}}
+        # HBM bytes of the dominant kernel's launches, from counter passes of this very command (None without rocprofv3)
+        traffic = tsrc = None
+        if rank == 0 and world == 1 and a.sketch == "gaussian" and not os.environ.get("STRUMPACK_AMD_BENCH_INNER"):
+            extra = ["--size", str(n), "--leaf", str(a.leaf), "--rel-tol", str(a.rel_tol), "--nrhs", str(a.nrhs), "--operand", a.operand]
+            if a.factor_ahead:
+                extra.append("--factor-ahead")
+            if a.symmetric:
+                extra.append("--symmetric")
+            # the MAIN launches of both sketch products: sketch_kernel<rows / 64, transposed?, group 0>
+            tmain = measure_traffic(extra, r"sketch_kernel<\d, (true|false), 0, (true|false)>")
+            if tmain is not None:
+                traffic = tmain["bytes"]
+                tsrc = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE passes of this command (one step each), main launches of "
+                        "sketch_kernel<3, ., 0>: read %.1f GB (FETCH_SIZE x 2, the guide's gfx950 correction) + written %.2f GB per launch"
+                        % (tmain["read_bytes"] * 1e-9, tmain["write_bytes"] * 1e-9))
+        if traffic is not None:
+            out["roofline"].update(traffic=traffic, traffic_source=tsrc)
+        if world > 1:
+            # diagnostic step with synchronised collectives: host-visible time of the compression's collectives
+            os.environ["STRUMPACK_AMD_TIME_COMM"] = "1"
+            H.destroy()
+            H = step()
+            out["comm_s"] = {"compress_collectives_synchronised": H.stats()["t_comm"], "note": "one extra step outside the timed region, every collective bracketed by stream synchronisations"}
+            del os.environ["STRUMPACK_AMD_TIME_COMM"]
     if rank == 0:
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(a.cpu_n, a.leaf, a.rel_tol)
-        elif not a.no_cpu_baseline:
+        elif a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = None
         print(json.dumps(out))
     H.destroy()

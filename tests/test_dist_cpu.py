@@ -272,7 +272,7 @@ def test_bench_dry_run_native_comm(world):
                OMP_NUM_THREADS="2", STRUMPACK_AMD_BENCH_COMM="rccl")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(29581 + world), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "0",
-           "--size", "800", "--leaf", "64", "--no-cpu-baseline"]
+           "--size", "800", "--leaf", "64", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -294,7 +294,7 @@ def test_bench_rendezvous_dry_run(world):
     env = dict(os.environ, STRUMPACK_AMD_BENCH_DRYRUN_LIB=emu_lib.PATH, HSSK_EMU_THREADS="2", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(29571 + world), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "1",
-           "--size", "1500", "--leaf", "64", "--no-cpu-baseline"]
+           "--size", "1500", "--leaf", "64", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -316,7 +316,7 @@ def test_bench_bare_gpus_spelling_spawns_the_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--size", "1500", "--leaf", "64", "--no-cpu-baseline"]
+           "--size", "1500", "--leaf", "64", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -347,3 +347,48 @@ def test_bench_refuses_silent_fallback():
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")], r.stdout
     assert "refusing to fall back" in r.stderr + r.stdout
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain one-rank bench run prints the headline line alone -- the checks, sweeps and CPU baseline are --full's -- and
+    --dump-outputs writes the solution of the last timed step, the same in two runs with the same arguments."""
+    import json
+    import numpy as np
+    import emu_lib
+    emu_lib.build()
+    env = dict(os.environ, STRUMPACK_AMD_BENCH_DRYRUN_LIB=emu_lib.PATH, HSSK_EMU_THREADS="2", OMP_NUM_THREADS="2")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    xs = []
+    for i in range(2):
+        out = tmp_path / ("out%d" % i)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+               "--size", "800", "--leaf", "64", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["metric"] == "hss_compress_ulv_factor_solve_gflops" and d["dtype"] == "f64" and d["higher_is_better"] is True
+        assert d["steps"] == 2 and d["warmup"] == 0 and d["ms_per_step"] > 0
+        assert not {"checks", "sweeps", "cpu_baseline", "comm_s"} & set(d), sorted(d)
+        x = np.load(str(out / "x.npy"))
+        assert x.dtype == np.float64 and x.shape == (800, 1) and np.isfinite(x).all() and np.abs(x).max() > 0
+        xs.append(x)
+    assert np.array_equal(xs[0], xs[1])
+
+
+def test_bench_dump_outputs_limit(tmp_path):
+    """--dump-outputs stays within 64 MB: an array beyond its share is written as a fixed sample of its rows, with the rows."""
+    import numpy as np
+    import bench
+    big = np.arange(9000000, dtype=np.float64).reshape(-1, 1)       # 72 MB
+    small = np.arange(6, dtype=np.int64).reshape(3, 2)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), {"x": big, "s": small})
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES
+    x, rows = np.load(str(tmp_path / "a" / "x.npy")), np.load(str(tmp_path / "a" / "x_rows.npy"))
+    assert x.dtype == np.float64 and rows.dtype == np.float64 and len(rows) > 1000 and np.array_equal(x[:, 0], rows)
+    assert np.array_equal(rows, np.load(str(tmp_path / "b" / "x_rows.npy")))
+    s = np.load(str(tmp_path / "a" / "s.npy"))
+    assert s.dtype == np.float64 and np.array_equal(s, small) and not (tmp_path / "a" / "s_rows.npy").exists()

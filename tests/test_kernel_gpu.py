@@ -112,7 +112,7 @@ def test_tsqr_staircase_matches_dense_sweep():
 
 
 @pytest.mark.parametrize("kern,h,dim,clus,rtol", [("Gauss", 1.3, 8, "cobble", 1e-2), ("Laplace", 2.0, 3, "kdtree", 1e-3), ("Gauss", 3.0, 20, "cobble", 1e-2)])
-def test_round6_front_end_against_the_forms_it_replaced(kern, h, dim, clus, rtol):
+def test_round6_front_end_against_the_forms_it_replaced(kern, h, dim, clus, rtol, tmp_path):
     """30000 points through the round-6 front end -- clustering on the device, the filtered neighbour search, the row ID from Gram
     matrices -- against the forms they replaced in a second process (host clustering, heap search, TSQR + register QRCP:
     STRUMPACK_AMD_CLUSTER_HOST / HSSK_KNN_FILTER / STRUMPACK_AMD_ID_GRAM): the same permutation, the same tree, ranks equal
@@ -137,7 +137,7 @@ def test_round6_front_end_against_the_forms_it_replaced(kern, h, dim, clus, rtol
     ) % (os.path.dirname(os.path.abspath(__file__)), os.path.dirname(os.path.dirname(os.path.abspath(__file__))), dim, rtol, kern, h, clus)
     out = []
     for mode, env in (("new", {}), ("old", {"STRUMPACK_AMD_CLUSTER_HOST": "1", "HSSK_KNN_FILTER": "0", "STRUMPACK_AMD_ID_GRAM": "0"})):
-        f = "/tmp/r06_front_%s_%s_%d.npz" % (mode, kern, dim)
+        f = str(tmp_path / ("front_%s.npz" % mode))
         r = subprocess.run([sys.executable, "-c", code, f], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         out.append(np.load(f))

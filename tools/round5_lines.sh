@@ -4,7 +4,7 @@
 tag=${1:-r05_lines}; out=/root/repo/gpurun_out/$tag; mkdir -p $out; cd /root/repo
 export STRUMPACK_AMD_BENCH_NO_PMC=1
 for cfg in "n1:--steps 10 --warmup 3" "kernel:--workload kernel --steps 4" "leaf512:--leaf 512" "nrhs64:--nrhs 64"; do
-  timeout 300 python bench.py --no-cpu-baseline ${cfg#*:} > $out/bench_${cfg%%:*}.json 2> $out/bench_${cfg%%:*}.err; echo "${cfg%%:*} rc=$?"
+  timeout 300 python bench.py --full --no-cpu-baseline ${cfg#*:} > $out/bench_${cfg%%:*}.json 2> $out/bench_${cfg%%:*}.err; echo "${cfg%%:*} rc=$?"
 done
 python - $out <<'PY'
 import json,sys,glob

@@ -5,7 +5,7 @@ tag=${1:-r05_tree}; out=/root/repo/gpurun_out/$tag; mkdir -p $out; cd /root/repo
 timeout 600 python -m pytest tests/test_hss_gpu.py -x -q -m gpu -k "one_launch or factor_ahead" > $out/pytest_tree.log 2>&1; echo "pytest rc=$?"; tail -3 $out/pytest_tree.log
 export STRUMPACK_AMD_BENCH_NO_PMC=1
 for mode in 1 0; do
-  STRUMPACK_AMD_TREE_LAUNCH=$mode timeout 300 python bench.py --no-cpu-baseline --steps 10 --warmup 3 > $out/bench_tree$mode.json 2> $out/bench_tree$mode.err; echo "bench tree=$mode rc=$?"
+  STRUMPACK_AMD_TREE_LAUNCH=$mode timeout 300 python bench.py --full --no-cpu-baseline --steps 10 --warmup 3 > $out/bench_tree$mode.json 2> $out/bench_tree$mode.err; echo "bench tree=$mode rc=$?"
 done
 cd /tmp; export TMPDIR=/tmp
 timeout 400 rocprofv3 --kernel-trace --stats -d $out/kt -o kt --output-format csv -- python /root/repo/bench.py --no-cpu-baseline --steps 3 --warmup 1 > $out/bench_under_rocprof.json 2> $out/kt.err

@@ -7,7 +7,7 @@ if [ -z "$2" ]; then
   timeout 1500 python -m pytest tests -x -q -m gpu --durations=8 > $out/pytest.log 2>&1; echo "pytest rc=$?"; tail -14 $out/pytest.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $out/smoke.log
 fi
-timeout 600 python bench.py > $out/bench_n1.json 2> $out/bench_n1.err; echo "bench n1 rc=$?"
+timeout 600 python bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err; echo "bench n1 rc=$?"
 cd /tmp; export TMPDIR=/tmp; export STRUMPACK_AMD_BENCH_NO_PMC=1
 timeout 400 rocprofv3 --kernel-trace --stats -d $out/kt -o kt --output-format csv -- python /root/repo/bench.py --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/kt.err
 python /root/repo/tools/trace_tail.py $out/kt > /dev/null 2>&1
@@ -28,7 +28,7 @@ timeout 300 python tools/cluster_ab.py > $out/cluster_ab.txt 2>&1; tail -2 $out/
 # secondary lines of the round (no counter passes, no CPU baseline)
 for cfg in "kernel:--workload kernel --steps 4" "leaf512:--leaf 512" "nrhs64:--nrhs 64" "generated:--operand generated" "symmetric:--symmetric" "factor_ahead:--factor-ahead" \
            "blr_front_200x200_root:--workload blr_front --front-n 200 --front-upd none --steps 3 --warmup 1" "blr_front_200x100:--workload blr_front --front-n 200 --front-ny 100 --steps 2 --warmup 1"; do
-  timeout 400 python bench.py --no-cpu-baseline ${cfg#*:} > $out/bench_${cfg%%:*}_n1.json 2> $out/bench_${cfg%%:*}.err; echo "${cfg%%:*} rc=$?"
+  timeout 400 python bench.py --full --no-cpu-baseline ${cfg#*:} > $out/bench_${cfg%%:*}_n1.json 2> $out/bench_${cfg%%:*}.err; echo "${cfg%%:*} rc=$?"
 done
 unset STRUMPACK_AMD_BENCH_NO_PMC
 timeout 400 python bench.py --workload blr_front --front-n 64 --steps 5 --warmup 2 > $out/bench_blr_front_n1.json 2> $out/bench_blr_front.err; echo "blr_front(dsep 4096, with the reference's CPU line) rc=$?"
