@@ -715,6 +715,10 @@ int hssk_sweep_require_mma(hssk_ctx* ctx, int on);
 int hssk_sweep_mma_min_nrhs(void);
 /* number of sweeps this process issued in the many-right-hand-side matrix-core form (kernels/hssk_sweep_mma.h) */
 long long hssk_sweep_mma_launches(void);
+/* number of single-launch sweeps this process issued (hssk_apply_sweep, hssk_ulv_fwd_sweep, hssk_ulv_bwd_sweep: vector and
+ * matrix-core forms), and of calls to them that returned 2 (nothing issued; the caller fell back to the batched launches) */
+long long hssk_sweep_fused_launches(void);
+long long hssk_sweep_fallbacks(void);
 /* Tinv (ceil(n/64) blocks of 64 x 64, leading dimension 64) = transposed inverses of the 64 x 64 diagonal blocks of the
  * triangular R (n x n, ldr), zero padded; see `mode`. */
 typedef struct hssk_trtri_desc {

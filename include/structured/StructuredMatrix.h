@@ -222,6 +222,10 @@ int SPX_d_struct_mult_child(const CSPStructMat S, int child, char trans, int m, 
  * out[b] (column-major, leading dimension ldo[b]); add != 0: is added to it.  on_device: out[b] are device pointers. */
 int SPX_d_struct_extract_blocks(const CSPStructMat S, int nb, const int* rows, const int* roff, const int* cols, const int* coff,
                                 double* const* out, const int* ldo, int add, int on_device);
+/* HSSMatrix<double>::write (HSS/HSSMatrix.hpp:501): the whole compressed representation to the file `path` -- per node in
+ * pre-order its dimensions, ranks and blocks D, B01, B10, XU, permU, Ir, XV, permV, Ic (layout: csrc/host/hss_io.cpp).  HSS only,
+ * single process. */
+int SPX_d_struct_write(const CSPStructMat S, const char* path);
 /* ---- BLR frontal matrix: partial factorization of F = [F11 F12; F21 F22] -- what the reference's sparse BLR fronts call,
  * BLR::BLRMatrix<T>::construct_and_partial_factor(A11, A12, A21, A22, B11, B12, B21, tiles1, tiles2, admissible, opts)
  * (BLR/BLRMatrix.hpp:186-194, BLR/BLRMatrix.cpp:740-1037, algorithm RL = its default; batched GPU precedent

@@ -34,7 +34,7 @@ SP_SYMBOLS = [
     "SPX_d_struct_from_dense_device_comm", "SPX_d_struct_from_blocks_device", "SPX_d_struct_from_blocks_device_cb",
     "SPX_d_struct_from_kernel_comm",
     "SPX_d_struct_from_generator", "SPX_d_struct_from_generator_comm", "SPX_d_struct_from_generator_sharded",
-    "SPX_d_struct_extract_blocks",
+    "SPX_d_struct_extract_blocks", "SPX_d_struct_write",
     "SPX_d_blr_front_factor", "SPX_d_blr_front_factor_device", "SPX_d_blr_front_time_phases", "SPX_blr_low_rank_algorithm", "SPX_d_blr_front_forward",
     "SPX_d_blr_front_backward", "SPX_d_blr_front_schur", "SPX_d_blr_front_schur_device", "SPX_d_blr_front_tile_ranks",
     "SPX_d_blr_front_stats", "SPX_d_blr_front_destroy",
@@ -122,6 +122,7 @@ def load(path):
     L.SPX_device_pool_set_limit_gb.restype = None
     ip = C.POINTER(C.c_int)
     L.SPX_d_struct_extract_blocks.argtypes = [vp, C.c_int, ip, ip, ip, ip, C.POINTER(C.c_void_p), ip, C.c_int, C.c_int]
+    L.SPX_d_struct_write.argtypes = [vp, C.c_char_p]
     L.SPX_d_blr_front_factor.argtypes = [C.POINTER(vp), C.c_int, C.c_int, dp, C.c_int, dp, C.c_int, dp, C.c_int, dp, C.c_int,
                                          C.c_int, ip, C.c_int, ip, C.c_char_p, C.POINTER(CSPOptions)]
     L.SPX_d_blr_front_factor_device.argtypes = [C.POINTER(vp), C.c_int, C.c_int, dp, ll, dp, ll, dp, ll, dp, ll,
@@ -403,6 +404,11 @@ class StructuredMatrix:
         if self.L.SPX_d_struct_extract_blocks(self.h, nb, ip(r), ip(roff), ip(c), ip(coff), ptrs, ip(ldo), int(add_to is not None), 0):
             raise RuntimeError("SPX_d_struct_extract_blocks failed")
         return out
+
+    def write(self, path):
+        """HSSMatrix::write: the compressed representation to a file (layout: csrc/host/hss_io.cpp)"""
+        if self.L.SPX_d_struct_write(self.h, str(path).encode()):
+            raise RuntimeError("SPX_d_struct_write failed")
 
     # ---- Schur complement of the (0,0) block (HSSMatrix::partial_factor / Schur_update / Schur_product_*) ----
     def partial_factor(self):

@@ -524,6 +524,13 @@ int SPX_d_struct_extract_blocks(const CSPStructMat S, int nb, const int* rows, c
   hss(S)->engine()->extract_blocks(0, nb, rows, roff, cols, coff, out, ldo, on_device != 0, add != 0);
   SP_CATCH
 }
+int SPX_d_struct_write(const CSPStructMat S, const char* path) {
+  SP_TRY
+  if (!hss(S)) throw std::invalid_argument("not an HSS matrix");
+  if (!path) throw std::invalid_argument("write: no file name");
+  hss(S)->write(path);
+  SP_CATCH
+}
 
 // ---- BLR frontal matrix (BLRMatrix::construct_and_partial_factor, BLR/BLRMatrix.cpp:740-1037) -------------------------
 extern "C++" {

@@ -847,8 +847,18 @@ int* sweep_err(hssk_ctx* ctx) {
 }  // namespace
 
 static std::atomic<long long> chain_launches{0};
+// single-launch sweeps issued (vector or matrix-core form), and sweeps that declined their operands (return code 2, nothing
+// issued: the caller takes the batched launches per level instead)
+static std::atomic<long long> fused_launches{0}, sweep_fallbacks{0};
+static int count_sweep(int rc) {
+  if (rc == 0) fused_launches++;
+  else if (rc == 2) sweep_fallbacks++;
+  return rc;
+}
 extern "C" long long hssk_sweep_mma_launches(void) { return mma_launches; }
 extern "C" long long hssk_sweep_chain_launches(void) { return chain_launches; }
+extern "C" long long hssk_sweep_fused_launches(void) { return fused_launches; }
+extern "C" long long hssk_sweep_fallbacks(void) { return sweep_fallbacks; }
 extern "C" int hssk_sweep_mma_min_nrhs(void) { return mma_min_nrhs() > 0 ? mma_min_nrhs() : 1 << 30; }
 extern "C" int hssk_sweep_require_mma(hssk_ctx* ctx, int on) { ctx->require_mma = on != 0; return 0; }
 
@@ -874,7 +884,7 @@ extern "C" int hssk_sweep_arm(hssk_ctx* ctx, double* buf, long long count) {
 
 extern "C" int hssk_sweep_chain_ok(int m, int r, int mv, int rv) { return chain_shape_ok(m, r, mv, rv, SW_MAX) ? 1 : 0; }
 
-extern "C" int hssk_ulv_fwd_sweep(hssk_ctx* ctx, const hssk_sweep_fwd_desc* descs, int count, int nrhs) {
+static int ulv_fwd_sweep(hssk_ctx* ctx, const hssk_sweep_fwd_desc* descs, int count, int nrhs) {
   HSSK_API_BEGIN
   if (count <= 0) return 0;
   if (nrhs < 1 || nrhs > SW_NR * 16384) HSSK_UNSUPPORTED("operands beyond the single-launch sweep");
@@ -944,7 +954,7 @@ extern "C" int hssk_ulv_fwd_sweep(hssk_ctx* ctx, const hssk_sweep_fwd_desc* desc
   HSSK_API_END
 }
 
-extern "C" int hssk_ulv_bwd_sweep(hssk_ctx* ctx, const hssk_sweep_bwd_desc* descs, int count, int nrhs) {
+static int ulv_bwd_sweep(hssk_ctx* ctx, const hssk_sweep_bwd_desc* descs, int count, int nrhs) {
   HSSK_API_BEGIN
   if (count <= 0) return 0;
   if (nrhs < 1 || nrhs > SW_NR * 16384) HSSK_UNSUPPORTED("operands beyond the single-launch sweep");
@@ -982,8 +992,8 @@ extern "C" int hssk_ulv_bwd_sweep(hssk_ctx* ctx, const hssk_sweep_bwd_desc* desc
   HSSK_API_END
 }
 
-extern "C" int hssk_apply_sweep(hssk_ctx* ctx, const hssk_apply_up_desc* ups, int nup, const hssk_apply_down_desc* downs,
-                                int ndown, int nrhs) {
+static int apply_sweep(hssk_ctx* ctx, const hssk_apply_up_desc* ups, int nup, const hssk_apply_down_desc* downs, int ndown,
+                       int nrhs) {
   HSSK_API_BEGIN
   if (nup + ndown <= 0) return 0;
   if (nrhs < 1 || nrhs > SW_NR * 16384) HSSK_UNSUPPORTED("operands beyond the single-launch sweep");
@@ -1038,6 +1048,17 @@ extern "C" int hssk_apply_sweep(hssk_ctx* ctx, const hssk_apply_up_desc* ups, in
   } else HSSK_LAUNCH((apply_sweep_kernel<SW_NR, SW_MAX, true>), dim3(nwg, gy), dim3(SW_T), lds(SW_NR, SW_MAX), ctx->stream, du, nup, dn, nrhs, sweep_err(ctx));
   hssk_rt::check_launch();
   HSSK_API_END
+}
+
+extern "C" int hssk_ulv_fwd_sweep(hssk_ctx* ctx, const hssk_sweep_fwd_desc* descs, int count, int nrhs) {
+  return count > 0 ? count_sweep(ulv_fwd_sweep(ctx, descs, count, nrhs)) : 0;
+}
+extern "C" int hssk_ulv_bwd_sweep(hssk_ctx* ctx, const hssk_sweep_bwd_desc* descs, int count, int nrhs) {
+  return count > 0 ? count_sweep(ulv_bwd_sweep(ctx, descs, count, nrhs)) : 0;
+}
+extern "C" int hssk_apply_sweep(hssk_ctx* ctx, const hssk_apply_up_desc* ups, int nup, const hssk_apply_down_desc* downs,
+                                int ndown, int nrhs) {
+  return nup + ndown > 0 ? count_sweep(apply_sweep(ctx, ups, nup, downs, ndown, nrhs)) : 0;
 }
 
 extern "C" int hssk_trtri_diag_vbatched(hssk_ctx* ctx, const hssk_trtri_desc* descs, int count) {

@@ -142,3 +142,32 @@ def test_symmetric_operand_hint(L):
     hk = K.Hssk(emu_lib.build())
     HC.check_symmetric_hint(L, hk, n=1024, leaf=64)
     hk.close()
+
+
+# ---- the sweeps against the generators of the compressed matrix (tests/hss_generators.py; the GPU tier: n up to 8192) --------
+GEN_OPS = HC.generator_operands("cpu")
+EMU_NRHS = (1, 12, 17, 65, 257)   # one count per route: fused vector form, hybrid, matrix-core (a tail group), beyond 64, batched
+
+
+@pytest.mark.parametrize("name", ["HSS_seq_1", "HSS_seq_5", "HSS_seq_11", "HSS_seq_14"])
+def test_generators_reference_is_exact(L, name, tmp_path):
+    HC.check_generators_credible(L, CASES[name], tmp_path / "h.bin")
+
+
+@pytest.mark.parametrize("name", sorted(GEN_OPS))
+def test_sweeps_against_generators_unsym(L, name, tmp_path):
+    from strumpack_amd import hssk as K
+    hk = K.Hssk(emu_lib.PATH)
+    H, n = HC.build_operand(L, hk, GEN_OPS[name])
+    assert H.is_compressed()
+    inner, ok = HC.chain_eligible(L, H)
+    full = name == "toeplitz_unsym"     # (every count once; the batched solve beyond 256 is the emulator's slowest path)
+    HC.check_against_generators(L, H, tmp_path / "h.bin", nrhs_list=HC.NRHS_ALL if full else EMU_NRHS,
+                                solve_nrhs=None if full else EMU_NRHS[:-1], hk=hk, chain=inner > 0 and ok == inner, shift_nrhs=(1,))
+    H.destroy()
+    hk.close()
+
+
+@pytest.mark.parametrize("variant", HC.ENV_VARIANTS)
+def test_env_switches_against_generators_unsym(variant, tmp_path):
+    HC.run_env_variant(emu_lib.build(), variant, tmp_path / "h.bin", 400, 32, timeout=300)

@@ -522,3 +522,46 @@ def test_inner_levels_in_one_launch_at_full_size(L, monkeypatch):
     Ac = 1.0 / (1.0 + np.abs(i[:, None] - cols[None, :]))
     # y = H b against A b on sampled ROWS (A symmetric): rows cols of A b
     assert np.linalg.norm(Ac.T @ b - res["1"][4][cols]) <= 1e2 * 1e-4 * np.linalg.norm(Ac.T @ b)
+
+
+# ---- the sweeps against the generators of the compressed matrix (tests/hss_generators.py) ------------------------------------
+GEN_OPS = HC.generator_operands("gpu")
+
+
+@pytest.mark.parametrize("name", ["HSS_seq_1", "HSS_seq_5", "HSS_seq_11", "HSS_seq_14", "config1_T4096_defaults"])
+def test_generators_reference_is_exact(L, name, tmp_path):
+    HC.check_generators_credible(L, CASES[name], tmp_path / "h.bin")
+
+
+@pytest.mark.parametrize("name", sorted(GEN_OPS))
+def test_sweeps_against_generators_unsym(L, name, tmp_path):
+    hk = K.Hssk(_loader.lib_path())
+    H, n = HC.build_operand(L, hk, GEN_OPS[name])
+    assert H.is_compressed()
+    inner, ok = HC.chain_eligible(L, H)
+    w = HC.check_against_generators(L, H, tmp_path / "h.bin", hk=hk, dev_nrhs=(1, 16, 64), chain=inner > 0 and ok == inner)
+    print("generators %s: n %d rank %d worst apply %.2e solve %.2e forward/cond %.2e" % (name, n, H.rank(), w["apply"], w["solve"],
+                                                                                       w["forward"]))
+    H.destroy()
+    hk.close()
+
+
+def test_env_switches_against_generators_unsym(tmp_path):
+    """each process-wide switch in a fresh child process of its own, one after another (a failing child ends the test: nothing
+    more is started)"""
+    for v in HC.ENV_VARIANTS:
+        HC.run_env_variant(_loader.lib_path(), v, tmp_path / "h.bin", 3000, 64, timeout=240)
+
+
+@pytest.mark.parametrize("kind,n,leaf", [(1, 100000, 256), (1, 100000, 512), (2, 32768, 256)])
+def test_full_size_against_generators_unsym(L, kind, n, leaf, tmp_path):
+    """the bench's step at full size (generated operand, rel_tol 1e-4, Philox samples): mult N / T and solve with 1 and 64
+    right-hand sides against the generators (the file is about 0.5 GB at N = 1e5; the solve held to the reference's own 1e-12,
+    test_HSS_seq.cpp)"""
+    o = capi.StructuredMatrix.options(L, rel_tol=1e-4, abs_tol=1e-8, leaf_size=leaf)
+    H = capi.StructuredMatrix.from_generator(L, n, kind, o, capi.StructuredMatrix.hss_options(L, random_engine="philox"))
+    assert H.is_compressed()
+    w = HC.check_against_generators(L, H, tmp_path / "h.bin", nrhs_list=(1, 64), shift=0.0, solve_bound=HC.SOLVE_TOLERANCE)
+    print("generators full size kind %d n %d leaf %d: rank %d worst apply %.2e solve %.2e" % (kind, n, leaf, H.rank(), w["apply"],
+                                                                                            w["solve"]))
+    H.destroy()
