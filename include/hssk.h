@@ -148,6 +148,31 @@ int hssk_dgemm(hssk_ctx* ctx, int transB, int m, long long n, long long k, doubl
                const double* A, long long lda, const double* B, long long ldb, double beta,
                double* C, long long ldc);
 
+/* ---- the same sketch for a SINGLE-PRECISION operand resident in HBM (FP32 matrix cores) -----------------
+ * hssk_dgemm with B a float matrix (ldb in floats); A (the engine's R^T panel), alpha, beta and C stay FP64.  For callers whose
+ * data is float: the operand is read where it lies, never widened as a whole (half the bytes of its promotion), and the
+ * products run on v_mfma_f32_32x32x2_f32, whose peak (157.3 TFLOP/s on gfx950) is twice the FP64 matrix rate.
+ * Arithmetic rules:
+ *   - A is rounded once to float (a zero-padded float copy of the panel, made by a small kernel in front of the product);
+ *   - products and sums run in FP32 on the matrix cores over one K-chunk (bitwise a k-ordered fmaf chain: one rounding
+ *     per product, FP32 accumulation);
+ *   - the K-chunks' partial tiles are widened and summed in FP64 in chunk order (the deterministic K-split, scratch and
+ *     reduce pass of hssk_dgemm);
+ *   - alpha, beta and the store into C are FP64;
+ *   - the result is bitwise equal from run to run.
+ * Error: |C - alpha fl32(A) op(B)| <= (k + 4) 2^-24 |alpha| |A| |op(B)| elementwise in the worst case (Higham's gamma_k with
+ * u = 2^-24; the chunks only shorten the chains); what rounding does in practice is ~ sqrt(k) u relative to |A| |op(B)|, about
+ * 6e-6 at k = 1e5.  All shapes are taken: interior tiles (whole 64 columns, k a multiple of 16, B 16-byte aligned, ldb a multiple
+ * of 4) by an unmasked kernel, the rest by a masked one.  Fills the timing bracket of hssk_dgemm (hssk_last_dgemm_ms / _flops,
+ * hssk_dgemm_timing_defer / _collect); hssk_last_dgemm_trace / _clock_ghz have nothing to report after it. */
+int hssk_sgemm_sketch(hssk_ctx* ctx, int transB, int m, long long n, long long k, double alpha,
+                      const double* A, long long lda,      /* m x k, FP64 */
+                      const float* B, long long ldb,       /* the operand; op(B) as in hssk_dgemm */
+                      double beta, double* C, long long ldc);
+/* dst(i, j) = (float) src(i, j) for a rows x cols block: the inverse of hssk_expand_image(..., HSSK_DT_F32).  ldd in floats, lds in
+ * doubles.  Compute stream. */
+int hssk_narrow_f32(hssk_ctx* ctx, float* dst, long long ldd, const double* src, long long lds, long long rows, long long cols);
+
 /* ---- operands given by a formula: the matrix is never stored ---------------------------------
  * (the reference's counterpart: the blocked sampler that evaluates tiles of an element routine on the fly,
  * structured/StructuredMatrix.cpp:214-262; here the tiles are evaluated INSIDE the sketch kernel, straight into the LDS
@@ -298,6 +323,9 @@ typedef struct hssk_elem_desc {
   int rlo, rhi, clo, chi;
 } hssk_elem_desc;
 int hssk_gather_elems(hssk_ctx* ctx, const hssk_elem_desc* descs, int count);
+/* hssk_gather_elems from a single-precision matrix: descs[].A points at floats, lda counts floats; same struct, same ownership
+ * windows; B is written as double (the entries widened one by one, exactly) */
+int hssk_gather_elems_f32(hssk_ctx* ctx, const hssk_elem_desc* descs, int count);
 /* B(i,j) = G(I[i], J[j]): hssk_gather_elems with the matrix replaced by the formula (descs[].A / lda are ignored) */
 int hssk_gen_elems(hssk_ctx* ctx, const hssk_gen* g, const hssk_elem_desc* descs, int count);
 /* out[0:count) = sum over g < nslab of slabs[g * stride + (0:count)]  (partial blocks of several ranks after an all-gather) */
@@ -521,7 +549,7 @@ typedef struct hssk_elem_src {   /* where scattered entries of the operand come 
   const double* A;
   long long lda;
   hssk_gen gen;
-  int use_gen;
+  int use_gen;   /* 0: A (doubles); 1: the formula; 2: A points at FLOATS (lda in floats), entries widened one by one */
 } hssk_elem_src;
 int hssk_tree_inner(hssk_ctx* ctx, hssk_tnode* nodes, const int* order, int count, int d, int lds, int rcap, double rtol,
                     double atol, int max_rank, const hssk_elem_src* src, int* res);

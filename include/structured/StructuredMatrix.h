@@ -65,7 +65,10 @@ int SP_d_struct_shift(CSPStructMat S, double s);
  * distinct per precision (a matrix made by SP_z_struct_from_dense must only go to SP_z_struct_* routines).  These
  * instantiations are carried by the double-precision MI355X engine: float is promoted to double, a complex matrix is
  * compressed through its interleaved real image (see csrc/host/HSSMatrixPromoted.hpp), so a complex caller's vectors are
- * used in place.  SP_?_struct_rank reports ranks in the caller's scalar type. */
+ * used in place.  What is native single precision: the sketch of a float operand that already lies in HBM
+ * (SPX_s_struct_from_dense_device below: FP32 matrix cores, the operand never widened as a whole); tree pass, factorization,
+ * solve and mat-vec of such a matrix are the double-precision engine as well.  SP_?_struct_rank reports ranks in the caller's
+ * scalar type. */
 #define SPX_DECLARE_C_API(P, CT)                                                                                        \
   void SP_##P##_struct_default_options(CSPOptions* opts);                                                               \
   void SP_##P##_struct_destroy(CSPStructMat* S);                                                                        \
@@ -113,6 +116,27 @@ int SPX_d_struct_from_dense_hss(CSPStructMat* S, int rows, int cols, const doubl
 /* A is a DEVICE pointer (column-major, ldA); nothing is copied, A is borrowed for the call */
 int SPX_d_struct_from_dense_device(CSPStructMat* S, int rows, int cols, const double* dA, long long ldA,
                                    const CSPOptions* opts, const SPXHSSOptions* h);
+/* The same for a SINGLE-PRECISION operand: dA is a DEVICE pointer to a column-major float matrix (ldA in floats), borrowed for
+ * the call and read where it lies -- a float caller whose matrix is already in HBM need not widen it (n^2 x 8 bytes more) to
+ * use the device entry.  *S is an ordinary SP_s_ handle: SP_s_struct_mult / factor / solve / shift / rank / memory / nonzeros /
+ * destroy work on it as on one made by SP_s_struct_from_dense, and the options are resolved as there (h may be NULL).
+ * sketch_precision selects how the two sketch products A R and A^T R are computed:
+ *   1  on the FP32 matrix cores (v_mfma_f32_32x32x2_f32, twice the FP64 matrix rate): the random panel is rounded once to
+ *      float, products and sums run in FP32 over one K-chunk, the chunks are summed in FP64, the samples are FP64;
+ *   2  exact: column panels of at most 1 GB are widened to double and multiplied in FP64 -- the results of
+ *      SP_s_struct_from_dense without the host link;
+ *   0  auto: 1 iff rel_tol >= (n + 4) 2^-24, the worst-case error unit of an FP32 dot product of length n (6e-3 at n = 1e5,
+ *      so the float default rel_tol = 1e-2 takes the matrix cores).  The rule is conservative: rounding in practice adds
+ *      ~ sqrt(n) 2^-24 (6e-6 relative at n = 1e5), and a caller who knows that may ask for 1 at rel_tol = 1e-4.
+ * Leaf and coupling blocks are read from the float operand and widened entry by entry (exact) on either route.  Single GPU,
+ * Gaussian sketch.  Returns 1 (and leaves *S alone) for a type other than SP_TYPE_HSS, a non-square shape or an unknown
+ * sketch_precision. */
+int SPX_s_struct_from_dense_device(CSPStructMat* S, int rows, int cols, const float* dA, long long ldA,
+                                   const CSPOptions* opts, const SPXHSSOptions* h, int sketch_precision);
+/* how an SP_s_ handle was sketched: 0 promoted host path, 1 FP32 matrix cores, 2 widened panels */
+int SPX_s_struct_sketch_route(const CSPStructMat S);
+/* the 24 slots of SPX_d_struct_stats, of the double-precision matrix that carries an SP_s_ handle */
+int SPX_s_struct_stats(const CSPStructMat S, double* out);
 /* one process per GPU.  With 2^c ranks rank g owns the g-th subtree at depth c (its sketch columns,
  * compression, ULV factors and sweeps: no communication); the top of the tree is replicated after small
  * all-gathers of the cut nodes' reduced blocks.  allgather(user, dbuf, bytes_per_rank) must perform an

@@ -40,6 +40,7 @@ SP_SYMBOLS = [
     "SPX_d_blr_front_stats", "SPX_d_blr_front_destroy",
     "SPX_tree_pass_launches", "SPX_tree_pass_fallbacks",
     "SPX_device_pool_cached_bytes", "SPX_device_pool_limit_bytes", "SPX_device_pool_trim", "SPX_device_pool_set_limit_gb",
+    "SPX_s_struct_from_dense_device", "SPX_s_struct_sketch_route", "SPX_s_struct_stats",
 ]
 ELEM_CB = C.CFUNCTYPE(C.c_double, C.c_int, C.c_int)
 ALLGATHER_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_longlong)
@@ -140,6 +141,24 @@ def load(path):
     L.SPX_d_blr_front_stats.argtypes = [vp, C.POINTER(C.c_double)]
     L.SPX_d_blr_front_destroy.argtypes = [C.POINTER(vp)]
     L.SPX_d_blr_front_destroy.restype = None
+    # single-precision handles (SP_s_struct_*) and the float device-operand entry
+    L.SP_s_struct_default_options.argtypes = [C.POINTER(CSPOptions)]
+    L.SP_s_struct_default_options.restype = None
+    L.SP_s_struct_destroy.argtypes = [C.POINTER(vp)]
+    L.SP_s_struct_destroy.restype = None
+    for f in ("SP_s_struct_rows", "SP_s_struct_cols", "SP_s_struct_rank", "SP_s_struct_factor", "SPX_s_struct_sketch_route"):
+        getattr(L, f).argtypes = [vp]
+        getattr(L, f).restype = C.c_int
+    for f in ("SP_s_struct_memory", "SP_s_struct_nonzeros"):
+        getattr(L, f).argtypes = [vp]
+        getattr(L, f).restype = C.c_longlong
+    L.SP_s_struct_from_dense.argtypes = [C.POINTER(vp), C.c_int, C.c_int, dp, C.c_int, C.POINTER(CSPOptions)]
+    L.SP_s_struct_mult.argtypes = [vp, C.c_char, C.c_int, dp, C.c_int, dp, C.c_int]
+    L.SP_s_struct_solve.argtypes = [vp, C.c_int, dp, C.c_int]
+    L.SP_s_struct_shift.argtypes = [vp, C.c_float]
+    L.SPX_s_struct_from_dense_device.argtypes = [C.POINTER(vp), C.c_int, C.c_int, dp, C.c_longlong,
+                                                 C.POINTER(CSPOptions), C.POINTER(SPXHSSOptions), C.c_int]
+    L.SPX_s_struct_stats.argtypes = [vp, C.POINTER(C.c_double)]
     return L
 
 
@@ -243,6 +262,88 @@ class BLRFront:
             self.destroy()
         except Exception:
             pass
+
+
+class StructuredMatrixF32:
+    """Single-precision HSS matrix behind an SP_s_ handle (structured::StructuredMatrix<float>): vectors are float32.
+    from_dense_device takes a float matrix that already lies in HBM (SPX_s_struct_from_dense_device); options come from
+    StructuredMatrix.options / hss_options."""
+
+    def __init__(self, lib, handle, n):
+        self.L, self.h, self.n = lib, handle, n
+
+    @classmethod
+    def from_dense(cls, lib, A, opts):
+        A = np.asfortranarray(A, dtype=np.float32)
+        h = C.c_void_p()
+        if lib.SP_s_struct_from_dense(C.byref(h), A.shape[0], A.shape[1], A.ctypes.data, A.shape[0], C.byref(opts)):
+            raise RuntimeError("SP_s_struct_from_dense failed")
+        return cls(lib, h, A.shape[0])
+
+    @classmethod
+    def from_dense_device(cls, lib, dptr, n, lda, opts, hss=None, precision=0):
+        """dptr: device address of a column-major float32 matrix (lda in floats).  precision 0 auto, 1 FP32 matrix cores,
+        2 exact (widened panels)."""
+        h = C.c_void_p()
+        rc = lib.SPX_s_struct_from_dense_device(C.byref(h), n, n, dptr, lda, C.byref(opts),
+                                                C.byref(hss) if hss is not None else None, precision)
+        if rc:
+            raise RuntimeError("SPX_s_struct_from_dense_device failed")
+        return cls(lib, h, n)
+
+    def destroy(self):
+        if self.h:
+            self.L.SP_s_struct_destroy(C.byref(self.h))
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def mult(self, B, trans="N"):
+        B = np.asfortranarray(B, dtype=np.float32).reshape(self.n, -1, order="F")
+        Cm = np.zeros_like(B, order="F")
+        if self.L.SP_s_struct_mult(self.h, trans.encode(), B.shape[1], B.ctypes.data, self.n, Cm.ctypes.data, self.n):
+            raise RuntimeError("SP_s_struct_mult failed")
+        return Cm
+
+    def factor(self):
+        if self.L.SP_s_struct_factor(self.h):
+            raise RuntimeError("SP_s_struct_factor failed")
+
+    def solve(self, B):
+        X = np.array(B, dtype=np.float32, order="F").reshape(self.n, -1, order="F")
+        if self.L.SP_s_struct_solve(self.h, X.shape[1], X.ctypes.data, self.n):
+            raise RuntimeError("SP_s_struct_solve failed")
+        return X
+
+    def shift(self, s):
+        if self.L.SP_s_struct_shift(self.h, C.c_float(s)):
+            raise RuntimeError("SP_s_struct_shift failed")
+
+    def rows(self):
+        return self.L.SP_s_struct_rows(self.h)
+
+    def rank(self):
+        return self.L.SP_s_struct_rank(self.h)
+
+    def memory(self):
+        return self.L.SP_s_struct_memory(self.h)
+
+    def nonzeros(self):
+        return self.L.SP_s_struct_nonzeros(self.h)
+
+    def sketch_route(self):
+        """0 promoted host path, 1 FP32 matrix cores, 2 widened panels"""
+        return self.L.SPX_s_struct_sketch_route(self.h)
+
+    def stats(self):
+        out = (C.c_double * 24)()
+        if self.L.SPX_s_struct_stats(self.h, out):
+            raise RuntimeError("SPX_s_struct_stats failed")
+        return dict(zip(STAT_NAMES, list(out)))
 
 
 class StructuredMatrix:

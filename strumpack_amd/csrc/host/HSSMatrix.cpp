@@ -154,6 +154,10 @@ void HSSMatrix<double>::compress_device(const double* dA, long long lda, const o
   make_engine(opts, tree_.get());
   eng_->compress_dense_device(dA, lda);
 }
+void HSSMatrix<double>::compress_device_f32(const float* dA, long long lda, const opts_t& opts, int precision) {
+  make_engine(opts, tree_.get());
+  eng_->compress_dense_device_f32(dA, lda, precision);
+}
 void HSSMatrix<double>::compress_device_sharded(const double* dA, long long lda, const opts_t& opts, int world, int rank,
                                                 void (*fn)(void*, void*, long long), void* user) {
   compress_device_sharded(dA, lda, opts, callback_group(world, rank, fn, user));

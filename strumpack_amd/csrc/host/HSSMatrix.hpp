@@ -75,6 +75,9 @@ template <> class HSSMatrix<double> : public structured::StructuredMatrix<double
   const double* device_points_ = nullptr;   // set while the kernel constructor compresses: the points the device clustering left on the device
   // extension: A resident in HBM
   void compress_device(const double* dA, long long lda, const opts_t& opts);
+  // extension (HSSMatrixPromoted.hpp): this matrix carries a SINGLE-precision operand resident in HBM (lda in floats);
+  // precision 0 auto / 1 FP32 matrix cores / 2 exact (DeviceHSS::compress_dense_device_f32)
+  void compress_device_f32(const float* dA, long long lda, const opts_t& opts, int precision);
   // extension: one process per GPU (subtree ownership below the cut level, replicated top);
   // `allgather` is an in-place all-gather of a device buffer (RCCL)
   void compress_device_sharded(const double* dA, long long lda, const opts_t& opts, int world, int rank,

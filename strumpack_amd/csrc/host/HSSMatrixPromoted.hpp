@@ -2,7 +2,12 @@
 // of the reference (HSS/HSSMatrix.cpp:513-516) behind the same construct / mult / factor / solve surface, computed by
 // the double-precision device engine:
 //   float            -> promoted to double (the FP64 engine is the hot path of this library; results are at least as
-//                       accurate as a single-precision computation, the memory footprint is that of the double matrix);
+//                       accurate as a single-precision computation, the memory footprint is that of the double matrix).
+//                       What is NATIVE single precision: a float operand that already lies in HBM (compress_device) is
+//                       sketched where it lies, on the FP32 matrix cores (hssk_sgemm_sketch: FP32 products and sums per
+//                       K-chunk, FP64 across chunks) or, on the exact route, through widened panels of at most 1 GB; its
+//                       leaf and coupling blocks are widened entry by entry.  Tree pass, ID, ULV factorization, solve and
+//                       mat-vec stay the FP64 engine;
 //   complex<double>  -> the real image of A = Ar + i Ai with real and imaginary parts INTERLEAVED,
 //                         Ahat(2i+a, 2j+b) = [Ar_ij  -Ai_ij ; Ai_ij  Ar_ij](a, b),
 //                       a real 2n x 2n matrix with the same HSS structure (cluster sizes and ranks doubled).  With this
@@ -53,7 +58,18 @@ template <typename T> class HSSMatrixPromoted : public structured::StructuredMat
     // the operand crosses the link in its own format and is expanded to its image on the device
     const int dtype = std::is_same<T, float>::value ? 1 : std::is_same<T, std::complex<float>>::value ? 2 : 3;   // HSSK_DT_*
     H_->compress_image(A.data(), A.ld(), dtype, scaled(opts));
+    route_ = 0;
   }
+  // T = float only: the operand is a column-major float matrix in DEVICE memory (lda in floats), read where it lies.
+  // precision 1: sketch products on the FP32 matrix cores; 2: exact route (widened panels, the results of compress(A) above);
+  // 0: 1 iff rel_tol >= (n + 4) 2^-24 (DeviceHSS::compress_dense_device_f32 has the reasoning)
+  template <typename U = T, typename = typename std::enable_if<std::is_same<U, float>::value>::type>
+  void compress_device(const U* dA, long long lda, const opts_t& opts, int precision = 0) {
+    H_->compress_device_f32(dA, lda, scaled(opts), precision);
+    route_ = H_->engine()->sketch_route();
+  }
+  // how the last compression sketched: 0 promoted host path, 1 FP32 matrix cores, 2 widened panels
+  int sketch_route() const { return route_; }
   void compress(const elem_t& Aelem, const opts_t& opts) {
     // block evaluation of the image from block evaluations of A
     typename HSSMatrix<double>::elem_t img = [&](const std::vector<std::size_t>& I, const std::vector<std::size_t>& J, DenseMatrix<double>& B) {
@@ -74,6 +90,7 @@ template <typename T> class HSSMatrixPromoted : public structured::StructuredMat
         for (std::size_t i = 0; i < I.size(); i++) B(i, j) = image(Bt(ri[i], cj[j]), I[i] % W, J[j] % W);
     };
     H_->compress_from_elements(img, scaled(opts));
+    route_ = 0;
   }
 
   std::size_t rows() const override { return rows_; }
@@ -179,6 +196,7 @@ template <typename T> class HSSMatrixPromoted : public structured::StructuredMat
     H_.reset(new HSSMatrix<double>(doubled(base), scaled(o)));
   }
   std::size_t rows_ = 0, cols_ = 0;
+  int route_ = 0;
   std::unique_ptr<HSSMatrix<double>> H_;
 };
 

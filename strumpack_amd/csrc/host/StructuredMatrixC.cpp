@@ -7,6 +7,7 @@
 
 #include "BLRMatrix.hpp"
 #include "HSSMatrix.hpp"
+#include "HSSMatrixPromoted.hpp"
 #include "Comm.hpp"
 #include "Kernel.hpp"
 #include "StructuredMatrix.hpp"
@@ -46,8 +47,7 @@ StructuredOptions<double> get_options(const CSPOptions* o) {
   opts.set_verbose(o->verbose != 0);
   return opts;
 }
-HSS::HSSOptions<double> get_hss_options(const CSPOptions* o, const SPXHSSOptions* h) {
-  HSS::HSSOptions<double> ho(get_options(o));
+void apply_hss_options(HSS::HSSOptions<double>& ho, const SPXHSSOptions* h) {
   if (h) {
     ho.set_d0(h->d0); ho.set_dd(h->dd); ho.set_p(h->p);
     ho.set_compression_algorithm(h->compression_algorithm == 0 ? HSS::CompressionAlgorithm::ORIGINAL : (h->compression_algorithm == 2 ? HSS::CompressionAlgorithm::HARD_RESTART : HSS::CompressionAlgorithm::STABLE));
@@ -60,8 +60,19 @@ HSS::HSSOptions<double> get_hss_options(const CSPOptions* o, const SPXHSSOptions
     ho.set_factor_ahead(h->factor_ahead != 0);
     ho.set_symmetric_operand(h->symmetric_operand);
   }
+}
+HSS::HSSOptions<double> get_hss_options(const CSPOptions* o, const SPXHSSOptions* h) {
+  HSS::HSSOptions<double> ho(get_options(o));
+  apply_hss_options(ho, h);
   return ho;
 }
+// the options of an SP_s_ handle: through StructuredOptions<float> (tolerances rounded to float), as SP_s_struct_from_dense
+HSS::HSSOptions<double> get_hss_options_s(const CSPOptions* o, const SPXHSSOptions* h) {
+  HSS::HSSOptions<double> ho{to_double_options(get_options_t<float>(o))};
+  apply_hss_options(ho, h);
+  return ho;
+}
+inline HSS::HSSMatrix<float>* hss_s(const CSPStructMat S) { return S ? dynamic_cast<HSS::HSSMatrix<float>*>(matT<float>(S)) : nullptr; }
 #define SP_TRY try {
 #define SP_CATCH                                                      \
   }                                                                   \
@@ -127,7 +138,8 @@ int SP_d_struct_shift(CSPStructMat S, double s) {
 }
 
 // ---- single precision and complex entry points (reference StructuredMatrix.h:103-602, StructuredMatrixC.cpp:83-821):
-// same conventions as SP_d_*; carried by the double-precision device engine (HSSMatrixPromoted.hpp)
+// same conventions as SP_d_*; carried by the double-precision device engine (HSSMatrixPromoted.hpp); a float operand resident in
+// HBM has a native single-precision sketch (SPX_s_struct_from_dense_device below)
 #define SPX_C_API(P, T, CT, TOCPP, REAL)                                                                             \
   void SP_##P##_struct_default_options(CSPOptions* o) {                                                              \
     StructuredOptions<T> d;                                                                                          \
@@ -228,6 +240,37 @@ int SPX_d_struct_from_dense_device(CSPStructMat* S, int rows, int cols, const do
   std::unique_ptr<CStructMat> s(new CStructMat);
   s->S.reset(H.release());
   *S = s.release();
+  SP_CATCH
+}
+// ---- single-precision operand resident in HBM: an ordinary SP_s_ handle whose sketch ran from the float matrix where it lies
+int SPX_s_struct_from_dense_device(CSPStructMat* S, int rows, int cols, const float* dA, long long ldA, const CSPOptions* opts,
+                                   const SPXHSSOptions* h, int sketch_precision) {
+  SP_TRY
+  if (opts->type != SP_TYPE_HSS) throw std::invalid_argument("SPX_s_struct_from_dense_device requires type SP_TYPE_HSS");
+  if (rows != cols) throw std::invalid_argument("HSS compression only supported for square matrices.");
+  if (sketch_precision < 0 || sketch_precision > 2) throw std::invalid_argument("SPX_s_struct_from_dense_device: sketch_precision must be 0 (auto), 1 (FP32 matrix cores) or 2 (exact)");
+  auto ho = get_hss_options_s(opts, h);
+  std::unique_ptr<HSS::HSSMatrix<float>> H(new HSS::HSSMatrix<float>(rows, cols, ho));
+  H->compress_device(dA, ldA, ho, sketch_precision);
+  std::unique_ptr<CStructMatT<float>> s(new CStructMatT<float>);
+  s->S.reset(H.release());
+  *S = s.release();
+  SP_CATCH
+}
+int SPX_s_struct_sketch_route(const CSPStructMat S) { return hss_s(S) ? hss_s(S)->sketch_route() : 0; }
+int SPX_s_struct_stats(const CSPStructMat S, double* o) {
+  SP_TRY
+  if (!hss_s(S)) throw std::invalid_argument("not an HSS matrix");
+  const HSS::HSSMatrix<double>& Hd = hss_s(S)->carrier();
+  const HSS::PhaseStats& st = Hd.engine()->stats();
+  o[0] = st.t_compress; o[1] = st.t_sketch; o[2] = st.t_random; o[3] = st.t_tree; o[4] = st.t_factor;
+  o[5] = st.t_solve; o[6] = st.t_mult; o[7] = st.sketch_kernel_ms; o[8] = st.sketch_launches; o[9] = st.rounds;
+  o[10] = st.d_final; o[11] = st.f_sketch; o[12] = st.f_local; o[13] = st.f_reduce; o[14] = st.f_id;
+  o[15] = st.f_ortho; o[16] = st.f_ulv; o[17] = st.f_solve; o[18] = (double)Hd.engine()->factor_memory();
+  o[19] = st.sketch_kernel_flops;
+  o[20] = st.sketch_kernel_bytes;
+  o[21] = st.b_solve; o[22] = st.b_mult;
+  o[23] = st.t_comm;
   SP_CATCH
 }
 int SPX_d_struct_from_dense_device_sharded(CSPStructMat* S, int rows, int cols, const double* dA, long long ldA,

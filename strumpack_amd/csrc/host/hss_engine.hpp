@@ -128,6 +128,16 @@ class DeviceHSS {
 
   // ---- construction (compression) ----
   void compress_dense_device(const double* dA, long long lda);       // A resident in HBM
+  // A resident in HBM in SINGLE precision (lda in floats): the operand is read where it lies.  precision 1: the two sketch
+  // products run on the FP32 matrix cores (hssk_sgemm_sketch: FP32 products and sums per K-chunk, FP64 reduction, samples land
+  // in the FP64 sample panels); 2: exact route -- column panels of at most 1 GB are widened to double and multiplied with
+  // hssk_dgemm, the results of the promoted host path; 0: route 1 iff rel_tol >= (n + 4) 2^-24, the worst-case error unit of
+  // an FP32 dot product of length n (Higham's gamma_n, u = 2^-24: 6e-3 at n = 1e5 -- a conservative, stated rule, hundreds of
+  // times above what rounding does in practice, ~ sqrt(n) u = 6e-6 relative at n = 1e5; a caller who knows that asks for
+  // route 1 at rel_tol = 1e-4).  Leaf and coupling blocks are read from the float operand and widened entry by entry; tree
+  // pass, ID, ULV, solve and mat-vec are the FP64 engine.  Single GPU, Gaussian sketch.
+  void compress_dense_device_f32(const float* dA, long long lda, int precision);
+  int sketch_route() const { return f32_route_; }   // of the last compression: 0 not a device float operand, 1 / 2 as above
   // A in host memory: streamed through the device in column blocks, uploads overlapped with the sketch GEMMs; the full
   // matrix is never resident in HBM (the reference's element sampler never stores A either, StructuredMatrix.cpp:214-262)
   void compress_dense_host(const double* A, long long lda);
@@ -283,6 +293,7 @@ class DeviceHSS {
   mutable std::recursive_mutex op_mu_;
   struct Source;
   struct DenseDeviceSource;
+  struct DenseDeviceSourceF32;
   struct HostBlockSource;
   struct ShardedDenseSource;
   struct CallbackSource;
@@ -383,6 +394,7 @@ class DeviceHSS {
   double *Rt_ = nullptr, *Srt_ = nullptr, *Sct_ = nullptr;
   double *Srt0_ = nullptr, *Sct0_ = nullptr;   // hard restart: the samples as drawn (the tree levels update Srt_ / Sct_ in place)
   int dcap_ = 0;
+  int f32_route_ = 0;
   int attempt_ = 0;   // compression attempts so far (sources re-carve their work buffers after a restart)
   // cut-exchange buffers of the distributed compression (exchange_cut_compress), reused across the rounds of an attempt
   double* cut_buf_ = nullptr;

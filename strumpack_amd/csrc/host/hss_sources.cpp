@@ -80,6 +80,76 @@ struct DeviceHSS::DenseDeviceSource : DeviceHSS::Source {
   }
 };
 
+// Dense operand resident in HBM in SINGLE precision (DeviceHSS::compress_dense_device_f32): the matrix is never widened as a
+// whole.  route 1: both sketch products on the FP32 matrix cores (hssk_sgemm_sketch) straight from the float operand; route 2
+// (exact): column panels A(:, c0:c1) of at most 1 GB are widened into one work buffer and multiplied with hssk_dgemm,
+//   Sc(c0:c1, :) = A(:, c0:c1)^T R,   Sr(:, :) += A(:, c0:c1) R(c0:c1, :)
+// -- the products of the streamed host operand (HostBlockSource) without the link.  Scattered entries are gathered from the
+// float operand and widened one by one (exact) on either route, by extract() and by the single-launch tree pass.
+struct DeviceHSS::DenseDeviceSourceF32 : DeviceHSS::Source {
+  const float* dA;
+  long long lda;
+  int route;
+  double* dBuf = nullptr;   // route 2: the widened panel
+  long long nb = 0;
+  int gen = -1;             // compression attempt the panel was carved in (a restart resets the work arena)
+  int done_products_ = 2;
+  DenseDeviceSourceF32(const float* a, long long l, int r) : dA(a), lda(l), route(r) {}
+  bool extract_before_sample() const override { return true; }
+  bool device_elems(const DeviceHSS&, hssk_elem_src* e) const override {
+    e->A = reinterpret_cast<const double*>(dA); e->lda = lda; e->use_gen = 2;
+    return true;
+  }
+  int products(const DeviceHSS&) const override { return done_products_; }
+  double sketch_flops(const DeviceHSS& H, int dn) const override { return 2.0 * done_products_ * (double)H.n_ * (double)H.n_ * dn; }
+  void sample(DeviceHSS& H, int r0, int dn) override {
+    if (H.o_.world > 1) throw std::invalid_argument("single-precision device operand: single-GPU only (multi-GPU float operands are not supported)");
+    if (H.sj_pat_) throw std::invalid_argument("single-precision device operand: the SJLT sketch is not supported; use the Gaussian sketch");
+    const long long N = H.n_;
+    if (N <= 0 || dn <= 0) return;
+    auto timed = [&](double bytes) {   // (read at the end of compress())
+      ck(hssk_dgemm_timing_defer(H.ctx_));
+      H.stats_.sketch_kernel_bytes += bytes;
+    };
+    if (route == 1) {
+      done_products_ = H.o_.symmetric ? 1 : 2;
+      ck(hssk_sgemm_sketch(H.ctx_, 1, dn, N, N, 1.0, H.Rt_ + r0, H.dcap_, dA, lda, 0.0, H.Srt_ + r0, H.dcap_));
+      timed(4.0 * (double)N * (double)N);
+      if (H.o_.symmetric) {   // A^T R = A R: the second product is a copy of the first
+        hssk_colgather_desc cp{H.Srt_ + r0, H.Sct_ + r0, nullptr, dn, (int)N, H.dcap_, H.dcap_, 0};
+        ck(hssk_gather_cols(H.ctx_, &cp, 1));
+      } else {
+        ck(hssk_sgemm_sketch(H.ctx_, 0, dn, N, N, 1.0, H.Rt_ + r0, H.dcap_, dA, lda, 0.0, H.Sct_ + r0, H.dcap_));
+        timed(4.0 * (double)N * (double)N);
+      }
+      return;
+    }
+    done_products_ = 2;
+    if (gen != H.attempt_) {
+      gen = H.attempt_;
+      // at most 1 GB of widened panel, whole 64-column tiles of the sketch GEMM
+      nb = std::max<long long>(64, (1LL << 30) / (8 * N) / 64 * 64);
+      nb = std::min(nb, (N + 63) / 64 * 64);
+      dBuf = H.work_->dbl((size_t)N * nb);
+    }
+    for (long long c0 = 0, b = 0; c0 < N; c0 += nb, b++) {
+      const long long c1 = std::min(N, c0 + nb);
+      ck(hssk_expand_image(H.ctx_, dBuf, N, dA + c0 * lda, lda, N, c1 - c0, HSSK_DT_F32));
+      ck(hssk_dgemm(H.ctx_, 0, dn, c1 - c0, N, 1.0, H.Rt_ + r0, H.dcap_, dBuf, N, 0.0, H.Sct_ + r0 + c0 * H.dcap_, H.dcap_));
+      timed(0.);
+      ck(hssk_dgemm(H.ctx_, 1, dn, N, c1 - c0, 1.0, H.Rt_ + r0 + c0 * H.dcap_, H.dcap_, dBuf, N, b ? 1.0 : 0.0, H.Srt_ + r0, H.dcap_));
+      timed(0.);
+    }
+  }
+  void extract(DeviceHSS& H, const std::vector<ElemReq>& reqs) override {
+    std::vector<hssk_elem_desc> d;
+    d.reserve(reqs.size());
+    for (auto& r : reqs)
+      if (r.m > 0 && r.n > 0) d.push_back(hssk_elem_desc{reinterpret_cast<const double*>(dA), lda, r.dI, r.dJ, r.i0, r.j0, r.dB, r.m, r.n, r.ldb, 0});
+    if (!d.empty()) ck(hssk_gather_elems_f32(H.ctx_, d.data(), (int)d.size()));
+  }
+};
+
 // Sharded dense operand (one process per GPU, subtree ownership): this rank holds the columns [j0, j1) of its subtree
 // (n x nloc) and, optionally, the rows [j0, j1) (nloc x n) -- never the whole matrix.
 //   sketch:  Sc(j0:j1, :) = A(:, j0:j1)^H R                                   -- local
@@ -492,6 +562,18 @@ void DeviceHSS::check_symmetry(Source& src) {
 
 void DeviceHSS::compress_dense_device(const double* dA, long long lda) {
   DenseDeviceSource s(dA, lda);
+  check_symmetry(s);
+  compress(s);
+}
+void DeviceHSS::compress_dense_device_f32(const float* dA, long long lda, int precision) {
+  if (precision < 0 || precision > 2) throw std::invalid_argument("compress_dense_device_f32: sketch precision must be 0 (auto), 1 (FP32 matrix cores) or 2 (exact)");
+  if (o_.world > 1) throw std::invalid_argument("compress_dense_device_f32: single-GPU only (multi-GPU float operands are not supported)");
+  if (o_.sketch == 1) throw std::invalid_argument("compress_dense_device_f32: the SJLT sketch is not supported on a float operand; use the Gaussian sketch");
+  if (!dA || lda < n_) throw std::invalid_argument("compress_dense_device_f32: bad operand");
+  // auto: gamma_n = (n + 4) 2^-24, the worst-case error unit of an FP32 dot product of length n, against the tolerance
+  const int route = precision ? precision : (o_.rel_tol >= ((double)n_ + 4.) * std::ldexp(1., -24) ? 1 : 2);
+  f32_route_ = route;
+  DenseDeviceSourceF32 s(dA, lda, route);
   check_symmetry(s);
   compress(s);
 }

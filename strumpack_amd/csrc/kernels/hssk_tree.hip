@@ -48,7 +48,9 @@ struct TreeParams {
 };
 
 __device__ __forceinline__ double tr_elem(const TreeParams& P, int i, int j) {
-  return P.use_gen ? hssk_gen_eval(P.gen, i, j) : hssk_gload(P.A, (size_t)i + (size_t)j * (size_t)P.lda);
+  if (P.use_gen == 1) return hssk_gen_eval(P.gen, i, j);
+  if (P.use_gen == 2) return (double)((const float*)P.A)[(size_t)i + (size_t)j * (size_t)P.lda];   // single-precision operand, widened
+  return hssk_gload(P.A, (size_t)i + (size_t)j * (size_t)P.lda);
 }
 
 // accumulate acc[j] += mk * C(j, k) over j < J for one k; C(j, k) = c[j * sj + k * sk] in the LDS (broadcast reads)
@@ -344,9 +346,10 @@ extern "C" int hssk_tree_inner(hssk_ctx* ctx, hssk_tnode* nodes, const int* orde
                                double atol, int max_rank, const hssk_elem_src* src, int* res) {
   HSSK_API_BEGIN
   if (count <= 0) return 0;
-  if (!src || (!src->use_gen && !src->A)) HSSK_UNSUPPORTED("no element source");
+  if (!src || (src->use_gen != 1 && !src->A)) HSSK_UNSUPPORTED("no element source");
+  if (src->use_gen < 0 || src->use_gen > 2) HSSK_UNSUPPORTED("unknown element source");
   if (d <= 0 || d > 256 || (rcap != 32 && rcap != 48 && rcap != 64)) HSSK_UNSUPPORTED("sample count / rank bound outside the kernel's variants");
-  if (src->use_gen && src->gen.kind != HSSK_GEN_TOEPLITZ && src->gen.kind != HSSK_GEN_TOEPLITZ_UPPER) HSSK_UNSUPPORTED("unknown generator kind");
+  if (src->use_gen == 1 && src->gen.kind != HSSK_GEN_TOEPLITZ && src->gen.kind != HSSK_GEN_TOEPLITZ_UPPER) HSSK_UNSUPPORTED("unknown generator kind");
   if (tree_lds_bytes(rcap) > hssk_rt::max_lds_per_workgroup()) HSSK_UNSUPPORTED("rank bound beyond this device's LDS");   // (the caller takes the level path)
   if (!ctx->h_sweep_err) { ctx->h_sweep_err = (int*)hssk_rt::pinned_malloc(64); *ctx->h_sweep_err = 0; }
   TreeParams P;

@@ -164,6 +164,7 @@ HSSK_SYMBOLS = [
     "hssk_plan_begin", "hssk_plan_end", "hssk_plan_replay", "hssk_plan_destroy", "hssk_plan_size",
     "hssk_sketch_gen", "hssk_gen_elems", "hssk_gen_fill", "hssk_colsets", "hssk_colsets_max_universe",
     "hssk_cluster_median", "hssk_pchol_id_vbatched", "hssk_pchol_id_max_m", "hssk_pchol_id_rank_cap", "hssk_sum_partials", "hssk_gram_vbatched", "hssk_gram_gen_vbatched", "hssk_gram_gen_supported",
+    "hssk_sgemm_sketch", "hssk_narrow_f32", "hssk_gather_elems_f32",
 ]
 
 
@@ -255,8 +256,13 @@ class Hssk:
         L.hssk_dgemm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong,
                                  C.c_double, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
                                  C.c_double, C.c_void_p, C.c_longlong]
+        # single-precision operand: A (R^T panel), C and the scalars are double, B points at floats (ldb in floats)
+        L.hssk_sgemm_sketch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong,
+                                        C.c_double, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
+                                        C.c_double, C.c_void_p, C.c_longlong]
+        L.hssk_narrow_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong]
         for name in ("hssk_gemm_vbatched", "hssk_gather_cols", "hssk_gather_rows",
-                     "hssk_gather_elems", "hssk_transpose", "hssk_id_vbatched", "hssk_qr_vbatched",
+                     "hssk_gather_elems", "hssk_gather_elems_f32", "hssk_transpose", "hssk_id_vbatched", "hssk_qr_vbatched",
                      "hssk_trsm_vbatched", "hssk_getrf_vbatched", "hssk_getrs_vbatched",
                      "hssk_sumsq_vbatched", "hssk_leaf_update_vbatched", "hssk_formq_vbatched",
                      "hssk_id_xsolve_vbatched", "hssk_gather_combine", "hssk_ulv_split", "hssk_tpqr_vbatched"):
