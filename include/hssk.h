@@ -277,6 +277,19 @@ long long hssk_colsets_max_universe(void);   /* largest universe hssk_colsets ta
 int hssk_cluster_median(hssk_ctx* ctx, double* X, int d, int n, int algo, int cluster_size, int* perm, int* status);
 /* pred[c] = sum_r w[r] k(x_r, t_c), c < m; T is d x m (device)   (Kernel::predict, kernel/KernelRegression.hpp:112-123) */
 int hssk_kernel_predict(hssk_ctx* ctx, const hssk_kernel_spec* spec, const double* w, const double* T, int m, double* pred);
+/* The promise of the single-precision prediction's matrix-core route: the worst relative error the norm expansion
+ * |x|^2 + |t|^2 - 2 x.t can add to a term w_r k(x_r, t_c).  A (training tile, test tile) pair whose scaled norms would exceed it,
+ * 4 (d + 4) 2^-24 (max |x~|^2 + max |t~|^2) > tau, is computed from FP32 differences instead. */
+#define HSSK_KPREDICT_TAU 1.220703125e-4 /* 2^-13 */
+/* pred[c] = sum_r w[r] k(x_r, t_c): float points (spec-like: X d x n, T d x m, device), float weights, float out;
+ * FP32 per pair, FP64 across pairs; bitwise repeatable.  d <= 64, ANOVA degree p <= min(8, d).  stats (host, 6 values, may be
+ * NULL; the call synchronises when given): [0] tiles (64 training x 64 test points) taken on the matrix cores, [1] tiles taken in
+ * the difference form, [2] splits of the training set, [3] device-clock microseconds of all launches, [4] of the main launch,
+ * [5] of the prep and reduce launches. */
+int hssk_kernel_predict_f32(hssk_ctx* ctx, const float* X, long long n, int d, int type, int p, double h,
+                            const float* w, const float* T, int m, float* pred, long long* stats);
+/* splits of the training set hssk_kernel_predict_f32 takes for n training and m test points: a function of (n, m) alone */
+int hssk_kernel_predict_splits(long long n, int m);
 
 /* ---- gathers / scatters ----------------------------------------------------------------------- */
 /* dst(:, j) = src(:, idx[j]) (idx == NULL: identity) -- DenseMatrix::extract_rows in the

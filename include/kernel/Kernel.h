@@ -23,6 +23,23 @@ void STRUMPACK_destroy_kernel_double(STRUMPACKKernel K);
 void STRUMPACK_kernel_fit_HSS_double(STRUMPACKKernel K, double* labels, int argc, char* argv[]);
 void STRUMPACK_kernel_predict_double(STRUMPACKKernel K, int m, double* test, double* prediction);
 
+/* Single precision, the reference's src/kernel/Kernel.h:45-80 (its Python estimator binds these for float32 data).  The fit is
+ * promoted: points and labels are widened exactly, the FP64 front end runs, the weights are rounded once to float; train and
+ * labels are reordered into cluster order in place.  Prediction is native FP32 on the device, from a model that stays in HBM
+ * between calls.  The SPX_ introspection calls below take either kind of handle. */
+STRUMPACKKernel STRUMPACK_create_kernel_float(int n, int d, float* train, float h, float lambda, int p, int type);
+void STRUMPACK_destroy_kernel_float(STRUMPACKKernel K);
+void STRUMPACK_kernel_fit_HSS_float(STRUMPACKKernel K, float* labels, int argc, char* argv[]);
+void STRUMPACK_kernel_predict_float(STRUMPACKKernel K, int m, float* test, float* prediction);
+/* the same prediction with test points (d x m, one point per column) and predictions (m) already in HBM, e.g. a torch tensor: no
+ * host copy of either; the work enqueued on the caller's stream must have finished, the result is complete on return.
+ * Non-zero: a pointer that is not a device pointer, no fit, or a double handle */
+int SPX_kernel_predict_device_float(STRUMPACKKernel K, int m, const float* dtest, float* dpred);
+/* the last float prediction of the handle: out[0] tiles (64 x 64 pairs) taken on the matrix cores, [1] tiles taken in the
+ * difference form, [2] splits of the training set, [3] device-clock microseconds of the prediction launches, [4] bytes uploaded
+ * by the call, [5] 1 if the model was already resident */
+int SPX_kernel_predict_stats(STRUMPACKKernel K, long long* out);
+
 /* ---- extensions (SPX_): introspection for tests / benchmarks --------------------------------------------- */
 /* after fit: out[0] compressed (0/1), [1] levels, [2] max rank, [3] memory bytes, [4] neighbour count used,
  * [5] compress us, [6] factor us, [7] solve us */

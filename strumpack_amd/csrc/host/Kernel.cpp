@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cstdlib>
 
+#include "DevicePool.hpp"
 #include "HSSMatrix.hpp"
 #include "NeighborSearch.hpp"
 #include "hssk.h"
@@ -101,6 +102,201 @@ std::vector<double> Kernel<double>::predict(const DenseMatrix<double>& test, con
   return prediction;
 }
 
+// ---- Kernel<float>: promoted fit, native FP32 prediction from a model that stays in HBM --------------------------------
+struct Kernel<float>::Resident {
+  hssk_ctx* ctx = nullptr;
+  float *dX = nullptr, *dw = nullptr;   // cluster-ordered points (d x n) and the weights of the last fit (device pool)
+  size_t bX = 0, bw = 0;
+  const float* src = nullptr;           // the host array dX is a copy of
+  size_t n = 0, d = 0;
+  bool have_w = false;
+  void drop() {
+    if (ctx && (dX || dw)) hssk_sync(ctx);
+    if (dX) DevicePool::get().release(dX, bX);
+    if (dw) DevicePool::get().release(dw, bw);
+    dX = dw = nullptr; bX = bw = 0; src = nullptr; have_w = false;
+  }
+  ~Resident() {
+    drop();
+    if (ctx) hssk_ctx_destroy(ctx);
+  }
+};
+
+namespace {
+struct PoolBuf {   // a device pool chunk for the length of a call
+  void* p = nullptr;
+  size_t bytes = 0;
+  hssk_ctx* ctx;
+  PoolBuf(hssk_ctx* c, size_t b) : bytes(std::max<size_t>(b, 256)), ctx(c) {
+    p = DevicePool::get().acquire(bytes);
+    if (!p) throw std::runtime_error(hssk_last_error());
+  }
+  ~PoolBuf() { hssk_sync(ctx); DevicePool::get().release(p, bytes); }
+};
+// a user-defined float kernel function in front of the FP64 front end (its points are exactly the widened floats)
+class PromotedUserKernel : public Kernel<double> {
+ public:
+  PromotedUserKernel(DenseMatrix<double>& data, const Kernel<float>& f) : Kernel<double>(data, f.lambda()), f_(f) {}
+
+ protected:
+  const Kernel<float>& f_;
+  double eval_kernel_function(const double* x, const double* y) const override {
+    std::vector<float> a(d()), b(d());
+    for (std::size_t i = 0; i < d(); i++) { a[i] = (float)x[i]; b[i] = (float)y[i]; }
+    return (double)f_.kernel_function(a.data(), b.data());
+  }
+};
+HSS::HSSOptions<double> widen(const HSS::HSSOptions<float>& o) {
+  HSS::HSSOptions<double> w;
+  w.set_rel_tol(o.rel_tol()); w.set_abs_tol(o.abs_tol()); w.set_leaf_size(o.leaf_size()); w.set_pivot_threshold(o.pivot_threshold());
+  w.set_max_rank(o.max_rank()); w.set_verbose(o.verbose());
+  w.set_d0(o.d0()); w.set_dd(o.dd()); w.set_p(o.p()); w.set_random_engine(o.random_engine());
+  w.set_random_distribution(o.random_distribution()); w.set_compression_algorithm(o.compression_algorithm());
+  w.set_compression_sketch(o.compression_sketch()); w.set_nnz0(o.nnz0()); w.set_nnz(o.nnz()); w.set_SJLT_algo(o.SJLT_algo());
+  w.set_user_defined_random(o.user_defined_random()); w.set_symmetric_operand(o.symmetric_operand());
+  w.set_factor_ahead(o.factor_ahead()); w.set_synchronized_compression(o.synchronized_compression()); w.set_log_ranks(o.log_ranks());
+  w.set_clustering_algorithm(o.clustering_algorithm()); w.set_approximate_neighbors(o.approximate_neighbors());
+  w.set_ann_iterations(o.ann_iterations()); w.set_neighbor_search(o.neighbor_search());
+  return w;
+}
+}  // namespace
+
+Kernel<float>::Kernel(DenseMatrix<float>& data, float lambda) : data_(data), lambda_(lambda) {}
+Kernel<float>::~Kernel() = default;
+bool Kernel<float>::fitted() const { return res_ && res_->have_w; }
+
+DenseMatrix<float> Kernel<float>::fit_HSS(std::vector<float>& labels, const HSS::HSSOptions<float>& opts) { return fit_HSS(labels, widen(opts)); }
+
+DenseMatrix<float> Kernel<float>::fit_HSS(std::vector<float>& labels, const HSS::HSSOptions<double>& opts) {
+  if (labels.size() != n()) throw std::invalid_argument("fit_HSS: one label per training point expected");
+  if (res_) res_->drop();
+  const std::size_t nn = n(), dd = d();
+  DenseMatrix<double> Xd(dd, nn);
+  for (std::size_t i = 0; i < nn; i++)
+    for (std::size_t j = 0; j < dd; j++) Xd(j, i) = (double)data_(j, i);
+  std::unique_ptr<Kernel<double>> Kd;
+  switch (device_type()) {
+    case 0: Kd.reset(new GaussKernel<double>(Xd, (double)width(), (double)lambda_)); break;
+    case 1: Kd.reset(new LaplaceKernel<double>(Xd, (double)width(), (double)lambda_)); break;
+    case 2: Kd.reset(new ANOVAKernel<double>(Xd, (double)width(), (double)lambda_, degree())); break;
+    default: Kd.reset(new PromotedUserKernel(Xd, *this));
+  }
+  if (neighbors()) Kd->set_neighbors(neighbors(), neighbor_count());
+  std::vector<double> ld(labels.begin(), labels.end());
+  DenseMatrix<double> wd = Kd->fit_HSS(ld, opts);
+  // the cluster order back into the caller's arrays (narrowing widened floats is exact), the solution rounded once
+  perm_ = Kd->permutation();
+  for (std::size_t i = 0; i < nn; i++) {
+    for (std::size_t j = 0; j < dd; j++) data_(j, i) = (float)Xd(j, i);
+    labels[i] = (float)ld[i];
+  }
+  DenseMatrix<float> w(nn, 1);
+  for (std::size_t i = 0; i < nn; i++) w(i, 0) = (float)wd(i, 0);
+  if (device_type() >= 0 && nn > 0) {
+    // the model stays in HBM: a prediction uploads test points only
+    if (!res_) res_.reset(new Resident());
+    Resident& R = *res_;
+    if (!R.ctx) {
+      int dev = 0;
+      if (const char* e = std::getenv("STRUMPACK_AMD_DEVICE")) dev = std::atoi(e);
+      ckk(hssk_ctx_create(&R.ctx, dev));
+    }
+    R.bX = sizeof(float) * dd * nn; R.bw = sizeof(float) * nn;
+    R.dX = (float*)DevicePool::get().acquire(R.bX);
+    R.dw = (float*)DevicePool::get().acquire(R.bw);
+    if (!R.dX || !R.dw) { R.drop(); throw std::runtime_error(hssk_last_error()); }
+    ckk(hssk_memcpy2d_h2d(R.ctx, R.dX, sizeof(float) * dd, data_.data(), sizeof(float) * data_.ld(), sizeof(float) * dd, (long long)nn));
+    ckk(hssk_memcpy_h2d(R.ctx, R.dw, w.data(), (long long)R.bw));
+    R.src = data_.data(); R.n = nn; R.d = dd; R.have_w = true;
+  }
+  return w;
+}
+
+// test points: on the host (test_host, leading dimension ldt) or in HBM (test_dev); weights: on the host, or null = the resident
+// ones; result to the host (out_host) or to HBM (out_dev)
+void Kernel<float>::run_predict(int m, const float* test_host, int ldt, const float* test_dev, const float* weights_host,
+                                float* out_host, float* out_dev) const {
+  for (auto& v : pstats_) v = 0;
+  if (m == 0) return;
+  const std::size_t nn = n(), dd = d();
+  if (!res_) res_.reset(new Resident());
+  Resident& R = *res_;
+  if (!R.ctx) {
+    int dev = 0;
+    if (const char* e = std::getenv("STRUMPACK_AMD_DEVICE")) dev = std::atoi(e);
+    ckk(hssk_ctx_create(&R.ctx, dev));
+  }
+  long long uploaded = 0;
+  const bool resident = R.dX && R.src == data_.data() && R.n == nn && R.d == dd;
+  if (!resident) {
+    R.drop();
+    R.bX = sizeof(float) * dd * nn;
+    R.dX = (float*)DevicePool::get().acquire(R.bX);
+    if (!R.dX) { R.drop(); throw std::runtime_error(hssk_last_error()); }
+    ckk(hssk_memcpy2d_h2d(R.ctx, R.dX, sizeof(float) * dd, data_.data(), sizeof(float) * data_.ld(), sizeof(float) * dd, (long long)nn));
+    R.src = data_.data(); R.n = nn; R.d = dd;
+    uploaded += (long long)R.bX;
+  }
+  if (!weights_host && !R.have_w) throw std::invalid_argument("predict: no fit");
+  std::unique_ptr<PoolBuf> wbuf, tbuf, pbuf;
+  const float* dw = R.dw;
+  if (weights_host) {
+    wbuf.reset(new PoolBuf(R.ctx, sizeof(float) * nn));
+    ckk(hssk_memcpy_h2d(R.ctx, wbuf->p, weights_host, (long long)(sizeof(float) * nn)));
+    uploaded += (long long)(sizeof(float) * nn);
+    dw = (const float*)wbuf->p;
+  }
+  const float* dT = test_dev;
+  if (!dT) {
+    tbuf.reset(new PoolBuf(R.ctx, sizeof(float) * dd * m));
+    ckk(hssk_memcpy2d_h2d(R.ctx, tbuf->p, sizeof(float) * dd, test_host, sizeof(float) * ldt, sizeof(float) * dd, m));
+    uploaded += (long long)(sizeof(float) * dd * m);
+    dT = (const float*)tbuf->p;
+  }
+  float* dp = out_dev;
+  if (!dp) { pbuf.reset(new PoolBuf(R.ctx, sizeof(float) * m)); dp = (float*)pbuf->p; }
+  long long st[6];
+  ckk(hssk_kernel_predict_f32(R.ctx, R.dX, (long long)nn, (int)dd, device_type(), degree(), (double)width(), dw, dT, m, dp, st));
+  if (out_host) ckk(hssk_memcpy_d2h(R.ctx, out_host, dp, (long long)(sizeof(float) * m)));
+  ckk(hssk_sync(R.ctx));
+  pstats_[0] = st[0]; pstats_[1] = st[1]; pstats_[2] = st[2]; pstats_[3] = st[3]; pstats_[4] = uploaded; pstats_[5] = resident ? 1 : 0;
+}
+
+std::vector<float> Kernel<float>::predict(const DenseMatrix<float>& test, const DenseMatrix<float>& weights) const {
+  if (test.rows() != d()) throw std::invalid_argument("predict: test points have the wrong dimension");
+  if (weights.rows() != n()) throw std::invalid_argument("predict: one weight per training point expected");
+  const int m = int(test.cols());
+  std::vector<float> prediction(m, 0.f);
+  if (m == 0) return prediction;
+  if (device_type() < 0) {
+    // a user-defined kernel function: the sums on the host, in float
+    for (int c = 0; c < m; c++) {
+      float s = 0.f;
+      for (std::size_t r = 0; r < n(); r++) s += weights(r, 0) * eval_kernel_function(data_.ptr(0, r), test.ptr(0, c));
+      prediction[c] = s;
+    }
+    return prediction;
+  }
+  run_predict(m, test.data(), test.ld(), nullptr, weights.data(), prediction.data(), nullptr);
+  return prediction;
+}
+
+std::vector<float> Kernel<float>::predict(const DenseMatrix<float>& test) const {
+  if (test.rows() != d()) throw std::invalid_argument("predict: test points have the wrong dimension");
+  if (!fitted()) throw std::invalid_argument("predict: no fit");
+  std::vector<float> prediction(test.cols(), 0.f);
+  run_predict(int(test.cols()), test.data(), test.ld(), nullptr, nullptr, prediction.data(), nullptr);
+  return prediction;
+}
+
+int Kernel<float>::predict_device(int m, const float* dtest, float* dpred) const {
+  if (!fitted() || m < 0) return 1;
+  if (m == 0) return 0;
+  if (!hssk_is_device_pointer(dtest) || !hssk_is_device_pointer(dpred)) return 2;
+  run_predict(m, nullptr, 0, dtest, nullptr, nullptr, dpred);
+  return 0;
+}
+
 const long long* last_fit_info() { return last_fit.v; }
 const std::vector<int>& last_fit_nodes() { return last_nodes; }
 
@@ -111,8 +307,13 @@ const std::vector<int>& last_fit_nodes() { return last_nodes; }
 using namespace strumpack;
 namespace {
 struct KernelRegression {
+  int precision = 0;   // the tag of the handle: 0 = double (K, training, weights), 1 = float (Kf, trainingf, weightsf)
   std::unique_ptr<kernel::Kernel<double>> K;
   DenseMatrix<double> training, weights;
+  std::unique_ptr<kernel::Kernel<float>> Kf;
+  DenseMatrix<float> trainingf, weightsf;
+  float* caller_train = nullptr;   // the float caller's array: reordered in place by the fit
+  bool any() const { return precision ? bool(Kf) : bool(K); }
   long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<int> nodes;   // node table of the last fit (6 ints per node)
 };
@@ -139,7 +340,7 @@ void STRUMPACK_destroy_kernel_double(STRUMPACKKernel K) { delete static_cast<Ker
 void STRUMPACK_kernel_fit_HSS_double(STRUMPACKKernel K, double* labels, int argc, char* argv[]) {
   try {
     auto kr = static_cast<KernelRegression*>(K);
-    if (!kr || !kr->K) throw std::invalid_argument("no kernel");
+    if (!kr || kr->precision != 0 || !kr->K) throw std::invalid_argument("no kernel");
     std::vector<double> vl(labels, labels + kr->K->n());
     HSS::HSSOptions<double> opts;
     opts.set_verbose(false);
@@ -153,11 +354,69 @@ void STRUMPACK_kernel_fit_HSS_double(STRUMPACKKernel K, double* labels, int argc
 void STRUMPACK_kernel_predict_double(STRUMPACKKernel K, int m, double* test, double* prediction) {
   try {
     auto kr = static_cast<KernelRegression*>(K);
-    if (!kr || !kr->K) throw std::invalid_argument("no kernel");
+    if (!kr || kr->precision != 0 || !kr->K) throw std::invalid_argument("no kernel");
     DenseMatrix<double> t(kr->K->d(), m, test, kr->K->d());
     auto pred = kr->K->predict(t, kr->weights);
     std::copy(pred.begin(), pred.end(), prediction);
   } catch (const std::exception& e) { report(e); }
+}
+
+STRUMPACKKernel STRUMPACK_create_kernel_float(int n, int d, float* train, float h, float lambda, int p, int type) {
+  try {
+    auto kr = new KernelRegression();
+    kr->precision = 1;
+    kr->caller_train = train;
+    kr->trainingf = DenseMatrix<float>(d, n, train, d);
+    switch (type) {
+      case 0: kr->Kf.reset(new kernel::GaussKernel<float>(kr->trainingf, h, lambda)); break;
+      case 1: kr->Kf.reset(new kernel::LaplaceKernel<float>(kr->trainingf, h, lambda)); break;
+      case 2: kr->Kf.reset(new kernel::ANOVAKernel<float>(kr->trainingf, h, lambda, p)); break;
+      default: std::cout << "ERROR: Kernel type not recognized!" << std::endl;
+    }
+    return kr;
+  } catch (const std::exception& e) { report(e); return nullptr; }
+}
+void STRUMPACK_destroy_kernel_float(STRUMPACKKernel K) { delete static_cast<KernelRegression*>(K); }
+
+void STRUMPACK_kernel_fit_HSS_float(STRUMPACKKernel K, float* labels, int argc, char* argv[]) {
+  try {
+    auto kr = static_cast<KernelRegression*>(K);
+    if (!kr || kr->precision != 1 || !kr->Kf) throw std::invalid_argument("no float kernel");
+    const std::size_t n = kr->Kf->n(), d = kr->Kf->d();
+    std::vector<float> vl(labels, labels + n);
+    HSS::HSSOptions<double> opts;   // (the promoted fit's options: tolerances do not pass through a float)
+    opts.set_verbose(false);
+    opts.set_clustering_algorithm(ClusteringAlgorithm::COBBLE);
+    opts.set_from_command_line(argc, argv);
+    kr->weightsf = kr->Kf->fit_HSS(vl, opts);
+    // the cluster order reaches the caller's arrays, as in the reference (which works on them in place)
+    std::copy(vl.begin(), vl.end(), labels);
+    if (kr->caller_train) std::copy(kr->trainingf.data(), kr->trainingf.data() + n * d, kr->caller_train);
+    std::copy(kernel::last_fit_info(), kernel::last_fit_info() + 8, kr->info);
+    kr->nodes = kernel::last_fit_nodes();
+  } catch (const std::exception& e) { report(e); }
+}
+void STRUMPACK_kernel_predict_float(STRUMPACKKernel K, int m, float* test, float* prediction) {
+  try {
+    auto kr = static_cast<KernelRegression*>(K);
+    if (!kr || kr->precision != 1 || !kr->Kf) throw std::invalid_argument("no float kernel");
+    DenseMatrix<float> t(kr->Kf->d(), m, test, kr->Kf->d());
+    auto pred = kr->Kf->predict(t);
+    std::copy(pred.begin(), pred.end(), prediction);
+  } catch (const std::exception& e) { report(e); }
+}
+int SPX_kernel_predict_device_float(STRUMPACKKernel K, int m, const float* dtest, float* dpred) {
+  try {
+    auto kr = static_cast<KernelRegression*>(K);
+    if (!kr || kr->precision != 1 || !kr->Kf) return 1;
+    return kr->Kf->predict_device(m, dtest, dpred);
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_predict_stats(STRUMPACKKernel K, long long* out) {
+  auto kr = static_cast<KernelRegression*>(K);
+  if (!kr || kr->precision != 1 || !kr->Kf) return 1;
+  std::copy(kr->Kf->predict_stats(), kr->Kf->predict_stats() + 6, out);
+  return 0;
 }
 int SPX_approximate_neighbors(int n, int d, const double* data, int iterations, int k, int* ann, double* scores) {
   try {
@@ -171,8 +430,9 @@ int SPX_approximate_neighbors(int n, int d, const double* data, int iterations, 
 }
 int SPX_kernel_set_neighbors(STRUMPACKKernel K, int k, const int* ann) {
   auto kr = static_cast<KernelRegression*>(K);
-  if (!kr || !kr->K) return 1;
-  kr->K->set_neighbors(ann, k);
+  if (!kr || !kr->any()) return 1;
+  if (kr->precision) kr->Kf->set_neighbors(ann, k);
+  else kr->K->set_neighbors(ann, k);
   return 0;
 }
 int SPX_kernel_node_info(STRUMPACKKernel K, int* out, int cap) {
@@ -190,12 +450,18 @@ int SPX_kernel_fit_info(STRUMPACKKernel K, long long* out) {
 }
 int SPX_kernel_permutation(STRUMPACKKernel K, int* perm) {
   auto kr = static_cast<KernelRegression*>(K);
-  if (!kr || !kr->K) return 1;
-  std::copy(kr->K->permutation().begin(), kr->K->permutation().end(), perm);
+  if (!kr || !kr->any()) return 1;
+  const std::vector<int>& pm = kr->precision ? kr->Kf->permutation() : kr->K->permutation();
+  std::copy(pm.begin(), pm.end(), perm);
   return 0;
 }
 int SPX_kernel_weights(STRUMPACKKernel K, double* w) {
   auto kr = static_cast<KernelRegression*>(K);
+  if (kr && kr->precision) {   // the float weights, widened
+    if (kr->weightsf.rows() == 0) return 1;
+    for (std::size_t i = 0; i < kr->weightsf.rows(); i++) w[i] = (double)kr->weightsf(i, 0);
+    return 0;
+  }
   if (!kr || kr->weights.rows() == 0) return 1;
   std::copy(kr->weights.data(), kr->weights.data() + kr->weights.rows(), w);
   return 0;

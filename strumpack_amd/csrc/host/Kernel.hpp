@@ -157,6 +157,138 @@ template <> class ANOVAKernel<double> : public Kernel<double> {
   }
 };
 
+// ---- single precision -------------------------------------------------------------------------------------------------
+// Same members as the double class.  The FIT is promoted: points and labels are widened exactly, the FP64 front end runs
+// unchanged (clustering, neighbours, compression, ULV, solve) and the solution is rounded once to float.  PREDICTION is
+// native FP32 on the device (hssk_kernel_predict_f32).  After a fit the cluster-ordered points and the weights stay in HBM
+// (device pool) until the next fit or the destructor: a prediction then uploads test points only.
+template <> class Kernel<float> {
+  using scalar_t = float;
+  using DenseM_t = DenseMatrix<float>;
+
+ public:
+  Kernel(DenseM_t& data, scalar_t lambda);
+  virtual ~Kernel();
+  Kernel(const Kernel&) = delete;
+  Kernel& operator=(const Kernel&) = delete;
+
+  std::size_t n() const { return data_.cols(); }
+  std::size_t d() const { return data_.rows(); }
+
+  virtual scalar_t eval(std::size_t i, std::size_t j) const {
+    return eval_kernel_function(data_.ptr(0, i), data_.ptr(0, j)) + ((i == j) ? lambda_ : scalar_t(0.));
+  }
+  void operator()(const std::vector<std::size_t>& I, const std::vector<std::size_t>& J, DenseM_t& B) const {
+    if (B.rows() != I.size() || B.cols() != J.size()) throw std::invalid_argument("Kernel::operator(): B has the wrong size");
+    for (std::size_t j = 0; j < J.size(); j++)
+      for (std::size_t i = 0; i < I.size(); i++) B(i, j) = eval(I[i], J[j]);
+  }
+
+  // labels and data() are permuted to the cluster order in place, as in the double class
+  DenseM_t fit_HSS(std::vector<scalar_t>& labels, const HSS::HSSOptions<scalar_t>& opts);
+  // extension: the promoted fit with its own (double) options, so that tolerances need not pass through a float
+  DenseM_t fit_HSS(std::vector<scalar_t>& labels, const HSS::HSSOptions<double>& opts);
+  // prediction[c] = sum_r weights(r) k(x_r, test_c); the weights are uploaded, the points only if data() is not the resident copy
+  std::vector<scalar_t> predict(const DenseM_t& test, const DenseM_t& weights) const;
+  // extensions: the same with the weights of the last fit, which are resident (test points are the only upload);
+  // predict_device: test (d x m) and prediction (m) already in HBM, no host copy of either; non-zero without a fit
+  std::vector<scalar_t> predict(const DenseM_t& test) const;
+  int predict_device(int m, const scalar_t* dtest, scalar_t* dpred) const;
+  bool fitted() const;
+  // of the last prediction: [0] tiles on the matrix cores, [1] tiles in the difference form, [2] splits of the training set,
+  // [3] device-clock microseconds of the launches, [4] bytes uploaded, [5] 1 if the model was already resident
+  const long long* predict_stats() const { return pstats_; }
+
+  const DenseM_t& data() const { return data_; }
+  DenseM_t& data() { return data_; }
+  std::vector<int>& permutation() { return perm_; }
+  const std::vector<int>& permutation() const { return perm_; }
+  virtual void permute() {}
+
+  scalar_t lambda() const { return lambda_; }
+  void set_neighbors(const int* ann, int k) { user_ann_.assign(ann, ann + (size_t)k * n()); user_k_ = k; }
+  const int* neighbors() const { return user_ann_.empty() ? nullptr : user_ann_.data(); }
+  int neighbor_count() const { return user_k_; }
+  virtual int device_type() const { return -1; }
+  virtual scalar_t width() const { return 1.f; }
+  virtual int degree() const { return 1; }
+  // the kernel function itself (what a user-defined subclass supplies)
+  scalar_t kernel_function(const scalar_t* x, const scalar_t* y) const { return eval_kernel_function(x, y); }
+
+ protected:
+  DenseM_t& data_;
+  scalar_t lambda_;
+  std::vector<int> perm_, user_ann_;
+  int user_k_ = 0;
+  virtual scalar_t eval_kernel_function(const scalar_t* x, const scalar_t* y) const = 0;
+
+ private:
+  struct Resident;   // device context, points and weights in HBM (Kernel.cpp)
+  mutable std::unique_ptr<Resident> res_;
+  mutable long long pstats_[6] = {0, 0, 0, 0, 0, 0};
+  void run_predict(int m, const scalar_t* test_host, int ldt, const scalar_t* test_dev, const scalar_t* weights_host,
+                   scalar_t* out_host, scalar_t* out_dev) const;
+};
+
+template <> class GaussKernel<float> : public Kernel<float> {
+ public:
+  GaussKernel(DenseMatrix<float>& data, float h, float lambda) : Kernel<float>(data, lambda), h_(h) {}
+  int device_type() const override { return 0; }
+  float width() const override { return h_; }
+
+ protected:
+  float h_;
+  float eval_kernel_function(const float* x, const float* y) const override {
+    float s = 0.f;
+    for (std::size_t i = 0; i < d(); i++) { float t = x[i] - y[i]; s += t * t; }
+    return std::exp(-s / (2.f * h_ * h_));
+  }
+};
+
+template <> class LaplaceKernel<float> : public Kernel<float> {
+ public:
+  LaplaceKernel(DenseMatrix<float>& data, float h, float lambda) : Kernel<float>(data, lambda), h_(h) {}
+  int device_type() const override { return 1; }
+  float width() const override { return h_; }
+
+ protected:
+  float h_;
+  float eval_kernel_function(const float* x, const float* y) const override {
+    float s = 0.f;
+    for (std::size_t i = 0; i < d(); i++) s += std::abs(x[i] - y[i]);
+    return std::exp(-s / h_);
+  }
+};
+
+template <> class ANOVAKernel<float> : public Kernel<float> {
+ public:
+  ANOVAKernel(DenseMatrix<float>& data, float h, float lambda, int p = 1) : Kernel<float>(data, lambda), h_(h), p_(p) {
+    if (p < 1 || p > int(d())) throw std::invalid_argument("ANOVAKernel: degree must be in [1, d]");
+  }
+  int device_type() const override { return 2; }
+  float width() const override { return h_; }
+  int degree() const override { return p_; }
+
+ protected:
+  float h_;
+  int p_;
+  float eval_kernel_function(const float* x, const float* y) const override {
+    std::vector<float> Kss(p_, 0.f), Kpp(p_ + 1);
+    for (std::size_t i = 0; i < d(); i++) {
+      const float t = x[i] - y[i], tmp = std::exp(-(t * t) / (2.f * h_ * h_));
+      float pw = tmp;
+      for (int j = 0; j < p_; j++) { Kss[j] += pw; pw *= tmp; }
+    }
+    Kpp[0] = 1.f;
+    for (int i = 1; i <= p_; i++) {
+      float s = 0.f;
+      for (int q = 1; q <= i; q++) s += ((q & 1) ? 1.f : -1.f) * Kpp[i - q] * Kss[q - 1];
+      Kpp[i] = s / i;
+    }
+    return Kpp[p_];
+  }
+};
+
 template <typename scalar_t>
 std::unique_ptr<Kernel<scalar_t>> create_kernel(KernelType k, DenseMatrix<scalar_t>& data, scalar_t h, scalar_t lambda, int p = 1) {
   switch (k) {

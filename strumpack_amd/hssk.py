@@ -165,6 +165,7 @@ HSSK_SYMBOLS = [
     "hssk_sketch_gen", "hssk_gen_elems", "hssk_gen_fill", "hssk_colsets", "hssk_colsets_max_universe",
     "hssk_cluster_median", "hssk_pchol_id_vbatched", "hssk_pchol_id_max_m", "hssk_pchol_id_rank_cap", "hssk_sum_partials", "hssk_gram_vbatched", "hssk_gram_gen_vbatched", "hssk_gram_gen_supported",
     "hssk_sgemm_sketch", "hssk_narrow_f32", "hssk_gather_elems_f32",
+    "hssk_kernel_predict_f32", "hssk_kernel_predict_splits",
 ]
 
 
@@ -277,6 +278,10 @@ class Hssk:
         L.hssk_kernel_eval_vbatched.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.hssk_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.hssk_kernel_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        # float points / weights / output; the last argument: 6 host long longs (may be None)
+        L.hssk_kernel_predict_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_double,
+                                              C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.hssk_kernel_predict_splits.argtypes = [C.c_longlong, C.c_int]
         L.hssk_colsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.hssk_cluster_median.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         for fn in ("hssk_pchol_id_vbatched", "hssk_sum_partials", "hssk_gram_vbatched"):
@@ -319,6 +324,22 @@ class Hssk:
         a = np.asarray(arr)
         d = DevArray(self, a.shape, dtype or a.dtype)
         return d.set(a)
+
+    def kernel_predict_f32(self, X, w, T, ktype, h, p=1, stats=False):
+        """sum_r w[r] k(x_r, t_c) for float32 points X (n x d) and T (m x d) through hssk_kernel_predict_f32: returns the m
+        float32 predictions (and the 6 statistics of include/hssk.h when stats is set)"""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        T = np.ascontiguousarray(T, dtype=np.float32)
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        (n, d), m = X.shape, T.shape[0]
+        dX, dT, dw, dp = (self.array(X.ravel()), self.array(T.ravel()), self.array(w), self.empty((m,), np.float32))
+        st = np.zeros(6, dtype=np.int64)
+        self.check(self.lib.hssk_kernel_predict_f32(self.ctx, dX.ptr, n, d, ktype, p, h, dw.ptr, dT.ptr, m, dp.ptr,
+                                                    st.ctypes.data if stats else None))
+        out = dp.get()
+        for a in (dX, dT, dw, dp):
+            a.free()
+        return (out, st) if stats else out
 
     def batch(self, fn_name, descs):
         if not descs:

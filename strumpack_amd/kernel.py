@@ -9,6 +9,8 @@ KERNEL_SYMBOLS = [
     "STRUMPACK_create_kernel_double", "STRUMPACK_destroy_kernel_double", "STRUMPACK_kernel_fit_HSS_double",
     "STRUMPACK_kernel_predict_double", "SPX_kernel_fit_info", "SPX_kernel_permutation", "SPX_kernel_weights",
     "SPX_clustering", "SPX_clustering_device", "SPX_kernel_node_info", "SPX_kernel_set_neighbors", "SPX_approximate_neighbors",
+    "STRUMPACK_create_kernel_float", "STRUMPACK_destroy_kernel_float", "STRUMPACK_kernel_fit_HSS_float",
+    "STRUMPACK_kernel_predict_float", "SPX_kernel_predict_device_float", "SPX_kernel_predict_stats",
 ]
 KERNEL_TYPES = {"Gauss": 0, "rbf": 0, "Laplace": 1, "ANOVA": 2}
 CLUSTERING = {"natural": 0, "2means": 1, "kdtree": 2, "pca": 3, "cobble": 4}
@@ -23,6 +25,13 @@ def load(path):
     L.STRUMPACK_destroy_kernel_double.argtypes = [vp]
     L.STRUMPACK_kernel_fit_HSS_double.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_char_p)]
     L.STRUMPACK_kernel_predict_double.argtypes = [vp, C.c_int, vp, vp]
+    L.STRUMPACK_create_kernel_float.restype = vp
+    L.STRUMPACK_create_kernel_float.argtypes = [C.c_int, C.c_int, vp, C.c_float, C.c_float, C.c_int, C.c_int]
+    L.STRUMPACK_destroy_kernel_float.argtypes = [vp]
+    L.STRUMPACK_kernel_fit_HSS_float.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_char_p)]
+    L.STRUMPACK_kernel_predict_float.argtypes = [vp, C.c_int, vp, vp]
+    L.SPX_kernel_predict_device_float.argtypes = [vp, C.c_int, vp, vp]
+    L.SPX_kernel_predict_stats.argtypes = [vp, vp]
     L.SPX_kernel_fit_info.argtypes = [vp, vp]
     L.SPX_kernel_permutation.argtypes = [vp, vp]
     L.SPX_kernel_weights.argtypes = [vp, vp]
@@ -39,29 +48,52 @@ class KernelRegression:
 
     def __init__(self, lib, h=1.0, lam=4.0, kernel="rbf", degree=1, argv=()):
         self.L, self.h, self.lam, self.ktype, self.p, self.argv = lib, h, lam, KERNEL_TYPES[kernel], degree, list(argv)
-        self.K = None
+        self.K, self.dtype = None, np.dtype(np.float64)
 
     def fit(self, X, y, neighbors=None):
-        X = np.ascontiguousarray(X, dtype=np.float64)     # n x d row-major == d x n column-major
-        y = np.ascontiguousarray(y, dtype=np.float64)
-        self.n, self.d = X.shape
+        """float32 X: the float entry points (promoted fit, FP32 prediction; the fit works on a copy of X, kept in cluster
+        order as self.X_); any other dtype: the double ones"""
         self.destroy()
-        self.K = self.L.STRUMPACK_create_kernel_double(self.n, self.d, X.ctypes.data, self.h, self.lam, self.p, self.ktype)
+        self.dtype = np.dtype(np.float32 if np.asarray(X).dtype == np.float32 else np.float64)
+        sfx = "float" if self.dtype == np.float32 else "double"
+        X = np.array(X, dtype=self.dtype, order="C")     # n x d row-major == d x n column-major
+        y = np.array(y, dtype=self.dtype, order="C")
+        self.n, self.d = X.shape
+        self.X_, self.y_ = X, y   # (the float entry points reorder both in place and keep pointing at X)
+        self.K = getattr(self.L, "STRUMPACK_create_kernel_" + sfx)(self.n, self.d, X.ctypes.data, self.h, self.lam, self.p, self.ktype)
         if not self.K:
-            raise RuntimeError("STRUMPACK_create_kernel_double failed")
+            raise RuntimeError("STRUMPACK_create_kernel_%s failed" % sfx)
         if neighbors is not None:   # tests: k x n lists in cluster order (see include/kernel/Kernel.h)
             nb = np.ascontiguousarray(neighbors, dtype=np.int32)
             self.L.SPX_kernel_set_neighbors(self.K, nb.shape[1], nb.ctypes.data)
         args = [b"kernel"] + [a.encode() for a in self.argv]
         argv = (C.c_char_p * len(args))(*args)
-        self.L.STRUMPACK_kernel_fit_HSS_double(self.K, y.ctypes.data, len(args), argv)
+        getattr(self.L, "STRUMPACK_kernel_fit_HSS_" + sfx)(self.K, y.ctypes.data, len(args), argv)
         return self
 
     def decision_function(self, T):
-        T = np.ascontiguousarray(T, dtype=np.float64)
-        out = np.zeros(T.shape[0])
-        self.L.STRUMPACK_kernel_predict_double(self.K, T.shape[0], T.ctypes.data, out.ctypes.data)
+        """T: m x d array; after a float32 fit also a float32 torch tensor on the device (m x d, contiguous), which is
+        read in place and answered by a tensor on the same device"""
+        if self.dtype == np.float32 and type(T).__module__.startswith("torch") and T.is_cuda:
+            import torch
+            if T.dtype != torch.float32 or not T.is_contiguous() or T.dim() != 2 or T.shape[1] != self.d:
+                raise ValueError("decision_function: a contiguous float32 m x d tensor is expected")
+            out = torch.empty(T.shape[0], dtype=torch.float32, device=T.device)
+            torch.cuda.synchronize(T.device)
+            if self.L.SPX_kernel_predict_device_float(self.K, T.shape[0], T.data_ptr(), out.data_ptr()):
+                raise RuntimeError("SPX_kernel_predict_device_float failed")
+            return out
+        T = np.ascontiguousarray(T, dtype=self.dtype)
+        out = np.zeros(T.shape[0], dtype=self.dtype)
+        sfx = "float" if self.dtype == np.float32 else "double"
+        getattr(self.L, "STRUMPACK_kernel_predict_" + sfx)(self.K, T.shape[0], T.ctypes.data, out.ctypes.data)
         return out
+
+    def predict_stats(self):
+        out = np.zeros(6, dtype=np.int64)
+        if self.L.SPX_kernel_predict_stats(self.K, out.ctypes.data):
+            raise RuntimeError("no float prediction")
+        return dict(zip(["mfma_tiles", "diff_tiles", "splits", "device_us", "uploaded_bytes", "resident"], out.tolist()))
 
     def predict(self, T):
         return np.where(self.decision_function(T) >= 0, 1.0, -1.0)
@@ -86,11 +118,11 @@ class KernelRegression:
         w = np.zeros(self.n)
         if self.L.SPX_kernel_weights(self.K, w.ctypes.data):
             raise RuntimeError("no fit")
-        return w
+        return w.astype(self.dtype)   # (a float handle hands out its float weights widened: narrowing them is exact)
 
     def destroy(self):
         if getattr(self, "K", None):
-            self.L.STRUMPACK_destroy_kernel_double(self.K)
+            getattr(self.L, "STRUMPACK_destroy_kernel_" + ("float" if self.dtype == np.float32 else "double"))(self.K)
             self.K = None
 
     def __del__(self):
