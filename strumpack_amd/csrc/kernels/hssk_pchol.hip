@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const hssk_gram_desc* __restr
 // The same product with ONE workgroup (8 waves) per panel and row chunk: the 16 x 16 tiles on and above the diagonal of the
 // whole m x m matrix are dealt to the waves in row-major runs (91 tiles for the 195-column panels of a leaf: 11 or 12 per wave --
 // the 128 x 128 blocks above left their waves 16, 16, 10 and 0 tiles of the same panel), every column of the chunk is staged once.
-// m <= 256 (NT tiles per wave: 5 up to 96 columns, 12 up to 208, 17 up to 256).
+// m <= 256 (NT tiles per wave: 5 up to 128 columns, 12 up to 208, 17 up to 256).
 namespace {
 constexpr int G2_K = 16, G2_KP = G2_K + 1, G2_T = 512;
 

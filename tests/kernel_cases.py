@@ -309,8 +309,12 @@ def case_gram_pchol_id(hk, problems, seed=41):
     """The ID of tall panels from their Gram matrix: hssk_gram_vbatched over row chunks + hssk_sum_partials give W^T W
     (against numpy), hssk_pchol_id_vbatched the pivots / rank / [R11 R12] of the column-pivoted QR with the reference's
     stopping rule (against LAPACK's QRCP of W itself), hssk_id_xsolve_vbatched the interpolation matrix.
-    problems: list of (d, m, rtol, atol, max_rank, numerical_rank or None, chunks)."""
+    problems: list of (d, m, rtol, atol, max_rank, numerical_rank or None, chunks).
+    The partial products and their sum have a leading dimension of m + 1 and are NaN-filled: row m must stay NaN.  On top of
+    the flat tolerance, entrywise |G - G_ref| <= (d + 2) u |W|^T |W| against the np.longdouble product (a sum of d products
+    whatever the chunking: a chunk of r rows and the sum of c partials round r + c - 1 <= d + 1 times).  Returns error / bound."""
     r = rng(seed)
+    worst = 0.0
     gd, sd, pd, keep = [], [], [], []
     for (d, m, rtol, atol, mr, nr, chunks) in problems:
         Wm = r.standard_normal((d, m)) if nr is None else _lowrank(r, d, m, nr) + 1e-9 * r.standard_normal((d, m))
@@ -320,11 +324,12 @@ def case_gram_pchol_id(hk, problems, seed=41):
         dW = hk.array(Wp)
         rows = -(-d // chunks)
         nch = -(-d // rows)
-        dP = hk.array(np.full((m * m * nch,), np.nan))
-        dG = hk.array(np.full((m + 2, m), np.nan))
+        ldg = m + 1
+        dP = hk.array(np.full((ldg * m * nch,), np.nan))
+        dG = None
         for c in range(nch):
             kr = min(rows, d - c * rows)
-            gd.append(K.GramDesc(dW.ptr + 8 * c * rows, ldw, kr, m, dP.ptr + 8 * c * m * m, m))
+            gd.append(K.GramDesc(dW.ptr + 8 * c * rows, ldw, kr, m, dP.ptr + 8 * c * ldg * m, ldg))
         cap = int(hk.lib.hssk_pchol_id_rank_cap(m))
         dperm, drank, dR = hk.empty((m,), np.int32), hk.empty((1,), np.int32), hk.array(np.full((cap, m), -3.0))
         keep.append((Wm, dW, dP, dG, dperm, drank, dR, cap, nch))
@@ -335,19 +340,28 @@ def case_gram_pchol_id(hk, problems, seed=41):
     for (prob, kp) in zip(problems, keep):
         d, m = prob[0], prob[1]
         Wm, dW, dP, dG, dperm, drank, dR, cap, nch = kp
-        dGc = hk.array(np.full((m * m,), np.nan))
+        dGc = hk.array(np.full(((m + 1) * m,), np.nan))
         outs.append(dGc)
-        sums.append(K.SumDesc(dP.ptr, m * m, m * m, nch, dGc.ptr))
+        sums.append(K.SumDesc(dP.ptr, (m + 1) * m, (m + 1) * m, nch, dGc.ptr))
     hk.batch("hssk_sum_partials", sums)
     hk.sync()
     for (prob, kp, dGc) in zip(problems, keep, outs):
         d, m, rtol, atol, mr, nr, chunks = prob
         Wm, dW, dP, dG, dperm, drank, dR, cap, nch = kp
-        G = dGc.get().reshape(m, m, order="F")
+        assert np.all(np.isnan(dP.get().reshape(m + 1, m * nch, order="F")[m])), "a partial product wrote into its padding row"
+        Gp = dGc.get().reshape(m + 1, m, order="F")
+        assert np.all(np.isnan(Gp[m])), "padding row of the Gram matrix"
+        G = Gp[:m]
         Gref = Wm.T @ Wm
         assert np.allclose(G, Gref, rtol=1e-12, atol=1e-12 * np.abs(Gref).max()), "Gram matrix"
         assert np.array_equal(G, G.T), "both triangles carry the same sums"
-        pd.append(K.PcholDesc(dGc.ptr, m, m, rtol, atol, mr, dperm.ptr, drank.ptr, dR.ptr, cap))
+        Wl = Wm.astype(np.longdouble)
+        err, bound = np.abs(G.astype(np.longdouble) - Wl.T @ Wl), (d + 2) * U53 * (np.abs(Wl).T @ np.abs(Wl))
+        frac = float((err / bound).max())
+        print("gram d=%d m=%d chunks=%d: largest error / bound %.3f" % (d, m, nch, frac))
+        assert np.all(err <= bound), "Gram matrix of %s: %d entries beyond the bound (worst %.3g x)" % (prob, int((err > bound).sum()), frac)
+        worst = max(worst, frac)
+        pd.append(K.PcholDesc(dGc.ptr, m + 1, m, rtol, atol, mr, dperm.ptr, drank.ptr, dR.ptr, cap))
     hk.batch("hssk_pchol_id_vbatched", pd)
     hk.sync()
     for (prob, kp) in zip(problems, keep):
@@ -384,19 +398,27 @@ def case_gram_pchol_id(hk, problems, seed=41):
         err = np.linalg.norm(Wm[:, perm[rank:]] - Wm[:, perm[:rank]] @ X) / np.linalg.norm(Wm)
         bound = max(rtol * dg[0], atol, dg[min(rank, min(d, m) - 1)]) * np.sqrt(m) * 4 / np.linalg.norm(Wm)
         assert err <= max(bound, 1e-7), f"ID residual {err} > {bound} for {prob}"
+    return worst
 
 
-def case_gram_gen(hk, n=700, d=6, seed=43):
+GRAM_GEN_SHAPES = ((333, 70, True), (64, 130, False), (17, 1, True), (500, 195, True), (2, 16, False))
+
+
+def case_gram_gen(hk, n=700, d=6, seed=43, shapes=GRAM_GEN_SHAPES, widths=(1.7, 2.2)):
     """hssk_gram_gen_vbatched: W^T W of blocks W = K(rows, cols) of a kernel matrix, evaluated while they are multiplied, against
-    numpy (index lists and ranges, row counts that are no multiple of the stage, Gauss and Laplace)."""
+    numpy (index lists and ranges, row counts that are no multiple of the stage, Gauss and Laplace).
+    shapes: one batch of (rows, m, index lists or ranges); widths: (Gauss, Laplace).  On top of the flat tolerance, entrywise
+    |G - G_ref| <= ((rows + 2) u + 2 eps) |W|^T |W| against the np.longdouble product of the np.longdouble entries, eps the
+    largest relative kernel_entry_bound of the block; the padding row m of the NaN-filled output stays NaN.  Returns error / bound."""
     r = rng(seed)
     X = r.standard_normal((n, d))
     dX = hk.array(X.T)
-    for (ktype, h) in ((0, 1.7), (1, 2.2)):
+    mmax, worst = max(sh[1] for sh in shapes), 0.0
+    for (ktype, h) in ((0, float(widths[0])), (1, float(widths[1]))):
         spec = K.KernelSpec(dX.ptr, n, d, ktype, 1, h, 3.0)
         assert hk.lib.hssk_gram_gen_supported(C.byref(spec), 256) == 1
         probs, descs, keep = [], [], []
-        for (rows, m, lists) in ((333, 70, True), (64, 130, False), (17, 1, True), (500, 195, True), (2, 16, False)):
+        for (rows, m, lists) in shapes:
             ri = r.permutation(n)[:rows].astype(np.int32)
             ci = r.permutation(n)[:m].astype(np.int32)
             r0, c0 = int(r.integers(0, n - rows)), int(r.integers(0, n - m))
@@ -413,13 +435,63 @@ def case_gram_gen(hk, n=700, d=6, seed=43):
         arr = (K.GramGenDesc * len(descs))(*descs)
         hk.check(hk.lib.hssk_gram_gen_vbatched(hk.ctx, C.byref(spec), arr, len(descs)))
         hk.sync()
+        frac = 0.0
         for (rr, cc, dG, m) in probs:
             W = kernel_np(X, rr, cc, ktype, h, 0.0)
-            G = dG.get()[:m]
+            Gp = dG.get()
+            assert np.all(np.isnan(Gp[m])), "gram_gen wrote into the padding row"
+            G = Gp[:m]
             assert np.allclose(G, W.T @ W, rtol=1e-12, atol=1e-13 * max(1.0, np.abs(W.T @ W).max())), (ktype, len(rr), m)
             assert np.array_equal(G, G.T)
+            Wl, a, _ = kernel_ref(X, rr, cc, ktype, h, 0.0)
+            GW = Wl.T @ Wl                                       # (W > 0: |W|^T |W| is the product itself)
+            eps = U53 * (8 + (d + 4) * float(a.max()))
+            err, bound = np.abs(G.astype(np.longdouble) - GW), ((len(rr) + 2) * U53 + 2 * eps) * GW
+            f = float((err / bound).max())
+            assert np.all(err <= bound), "gram_gen type %d d %d rows %d m %d (batch up to %d columns): %d entries beyond the bound (worst %.3g x)" % (
+                ktype, d, len(rr), m, mmax, int((err > bound).sum()), f)
+            frac = max(frac, f)
+        print("gram_gen type=%d d=%d mmax=%d: largest error / bound %.3f" % (ktype, d, mmax, frac))
+        worst = max(worst, frac)
     spec = K.KernelSpec(dX.ptr, n, d, 2, 2, 1.0, 0.0)
     assert hk.lib.hssk_gram_gen_supported(C.byref(spec), 100) == 0   # (ANOVA: evaluated by hssk_kernel_eval_vbatched)
+    return worst
+
+
+# The Gram kernels are instantiated for 5, 12 and 17 tiles (16 x 16) per wave and dispatched on the widest panel of a batch:
+# 5 up to 128 columns, 12 up to 208, 17 up to 256.  A wave that is handed more tiles than its instantiation holds drops them
+# without a sign, so every batch below has its widest panel on one side of a boundary.
+# hssk_gram_vbatched -- (rows, m, rtol, atol, max_rank, numerical rank, chunks), keyed by the widest panel
+GRAM_BATCHES = {
+    96: [(300, 40, 1e-3, 1e-12, 1000, 12, 1), (301, 96, 1e-4, 1e-12, 1000, 20, 3), (260, 1, 1e-2, 1e-12, 10, None, 1)],
+    128: [(300, 128, 1e-3, 1e-12, 1000, 20, 2), (261, 17, 1e-4, 1e-12, 5, 9, 1)],
+    129: [(300, 129, 1e-3, 1e-12, 1000, 20, 2), (270, 5, 1e-2, 1e-10, 1000, None, 1)],
+    208: [(420, 208, 1e-3, 1e-12, 1000, 30, 2), (300, 64, 1e-4, 1e-12, 1000, 15, 1)],
+    209: [(523, 209, 1e-3, 1e-12, 1000, 30, 3), (300, 17, 1e-4, 1e-12, 1000, 6, 1)],
+    256: [(600, 256, 1e-3, 1e-12, 1000, 40, 2), (523, 209, 1e-3, 1e-12, 1000, 30, 3), (300, 17, 1e-4, 1e-12, 1000, 6, 1)],
+    70: [(259, 70, 1e-3, 1e-12, 1000, 12, 7), (257, 33, 1e-4, 1e-12, 1000, 9, 128)],      # odd row counts, chunks of 37 and of 2 - 3 rows
+}
+# hssk_gram_gen_vbatched -- (rows, m, lists), keyed by the widest panel; row counts around the 16 rows of a stage, one row, one
+# column next to the widest panel
+GRAM_GEN_BATCHES = {
+    128: ((1, 128, True), (15, 1, False), (33, 96, True)),
+    129: ((16, 129, False), (2, 1, True)),
+    208: ((17, 208, True), (500, 1, False)),
+    209: ((33, 209, False), (15, 70, True)),
+    256: ((500, 256, True), (1, 1, False), (16, 200, False)),
+}
+GRAM_GEN_DIMS = (1, 15, 16)       # (6 is the dimension of the batches above; the row points are fetched by the threads < 16 d)
+GRAM_GEN_ROWS = ((1, 40, True), (2, 129, False), (15, 1, True), (16, 96, False), (17, 209, True), (33, 256, False), (500, 128, True))
+
+
+def case_gram_gen_batch(hk, mmax):
+    return case_gram_gen(hk, seed=400 + mmax, shapes=GRAM_GEN_BATCHES[mmax], widths=kernel_widths(6)[:2])
+
+
+def case_gram_gen_dims(hk, d):
+    w = kernel_widths(d)[:2]
+    return max(case_gram_gen(hk, d=d, seed=500 + d, shapes=GRAM_GEN_ROWS, widths=w),
+               case_gram_gen(hk, d=d, seed=600 + d, shapes=((33, 128, True), (16, 1, False)), widths=w))
 
 
 def case_qr(hk, shapes, seed=7):
@@ -668,23 +740,115 @@ def kernel_np(X, I, J, ktype, h, lam, p=1):
     return K + lam * (np.asarray(I)[:, None] == np.asarray(J)[None, :])
 
 
-def case_kernel_eval(hk, n=300, d=8, seed=21):
+U53 = 2.0 ** -53
+
+
+def kernel_ref(X, I, J, ktype, h, lam, p=1):
+    """kernel_np in np.longdouble, with what the error bound of an FP64 evaluation needs.  Returns (k, a, A):
+    k  the entry, lambda on the diagonal included;
+    a  the exponent's magnitude: |x-y|_2^2 / (2 h^2) (Gauss), |x-y|_1 / h (Laplace), the largest per-coordinate one (ANOVA);
+    A  the magnitude the rounding errors are relative to: the kernel value itself (Gauss, Laplace: > 0), for ANOVA the
+       recurrence with all signs positive (>= |k|: its alternating sum cancels), as kpredict_cases.reference has it."""
+    LD = np.longdouble
+    X = np.asarray(X, dtype=LD)
+    I, J = np.asarray(I), np.asarray(J)
+    h = LD(h)
+    k, a, A = (np.zeros((len(I), len(J)), dtype=LD) for _ in range(3))
+    step = int(max(1, 2_000_000 // max(1, len(J) * X.shape[1])))   # (rows per pass: the differences stay a few tens of MB)
+    for i0 in range(0, len(I), step):
+        df = X[I[i0:i0 + step]][:, None, :] - X[J][None, :, :]
+        sl = slice(i0, i0 + step)
+        if ktype == 0:
+            a[sl] = (df ** 2).sum(-1) / (2 * h * h)
+            k[sl] = A[sl] = np.exp(-a[sl])
+        elif ktype == 1:
+            a[sl] = np.abs(df).sum(-1) / h
+            k[sl] = A[sl] = np.exp(-a[sl])
+        else:
+            ai = df ** 2 / (2 * h * h)
+            t = np.exp(-ai)
+            Kss = [(t ** (j + 1)).sum(-1) for j in range(p)]
+            Kpp, App = [np.ones(t.shape[:2], dtype=LD)], [np.ones(t.shape[:2], dtype=LD)]
+            for i in range(1, p + 1):
+                Kpp.append(sum((-1) ** (s + 1) * Kpp[i - s] * Kss[s - 1] for s in range(1, i + 1)) / i)
+                App.append(sum(App[i - s] * Kss[s - 1] for s in range(1, i + 1)) / i)
+            a[sl], k[sl], A[sl] = ai.max(-1), Kpp[p], App[p]
+    return k + LD(lam) * (I[:, None] == J[None, :]), a, A
+
+
+def kernel_entry_bound(a, A, ktype, d, lam, p=1):
+    """Error bound of one FP64 kernel entry against kernel_ref (u = 2^-53; the bound of kpredict_cases with FP64's u):
+      Gauss / Laplace   u (8 + (d + 4) a) k + u |lambda|       the d-term sum and its scaling perturb the exponent a relatively
+                                                               by (d + 4) u, i.e. exp(-a) by (d + 4) a u; 8 u for exp and the sum
+      ANOVA             u (8 + p (d + 10 + 5 a_max)) A + u |lambda|"""
+    rel = (8 + (d + 4) * a) if ktype != 2 else (8 + p * (d + 10 + 5 * a))
+    return U53 * rel * A + U53 * abs(lam)
+
+
+def kernel_widths(d):
+    """kernel widths (Gauss, Laplace, ANOVA) that keep the entries of a standard normal cloud in R^d away from 0 and 1"""
+    return (0.9 * np.sqrt(d) + 0.4, 0.9 * d, 0.9 * np.sqrt(d) + 0.4)
+
+
+SENTINEL = -7.25
+
+
+def case_kernel_eval(hk, n=300, d=8, seed=21, kinds=((0, 1), (1, 1), (2, 1), (2, 3)), widths=None):
+    """hssk_kernel_eval_vbatched against kernel_ref under kernel_entry_bound: index lists and ranges, a whole tile, one row
+    over three column tiles; the outputs are pre-filled and the rows nr .. ldo - 1 of every column must come back bitwise.
+    widths: (Gauss, Laplace, ANOVA) kernel widths, None: 1.3 for all (and the flat tolerance of the first version of this
+    case on top of the bound).  Returns the largest error / bound."""
     r = rng(seed)
     X = r.standard_normal((n, d))
     dX = hk.array(X.T)                      # d x n, one point per column
-    for (ktype, p) in [(0, 1), (1, 1), (2, 1), (2, 3)]:
-        spec = K.KernelSpec(dX.ptr, n, d, ktype, p, 1.3, 3.11)
+    lam, worst = 3.11, 0.0
+    for (ktype, p) in kinds:
+        h = 1.3 if widths is None else float(widths[ktype])
+        spec = K.KernelSpec(dX.ptr, n, d, ktype, p, h, lam)
         I1, J1 = r.permutation(n)[:70].astype(np.int32), r.permutation(n)[:130].astype(np.int32)
         J1[:5] = I1[:5]                      # a few diagonal hits
         dI, dJ = hk.array(I1), hk.array(J1)
-        o1, o2 = hk.empty((70 + 3, 130)), hk.empty((65, 40))
-        descs = [K.KevalDesc(dI.ptr, dJ.ptr, o1.ptr, 70, 130, 73, 0, 0),
-                 K.KevalDesc(None, None, o2.ptr, 65, 40, 65, 100, 120)]   # ranges, overlapping -> diagonal entries
-        arr = (K.KevalDesc * 2)(*descs)
-        hk.check(hk.lib.hssk_kernel_eval_vbatched(hk.ctx, C.byref(spec), arr, 2))
+        # (rows, columns, ldo, row list, column list, r0, c0)
+        probs = [(70, 130, 73, I1, J1, 0, 0),
+                 (65, 40, 65, None, None, 100, 120),       # ranges, overlapping -> diagonal entries
+                 (64, 64, 67, None, None, 5, 5),           # exactly one tile, the whole diagonal
+                 (1, 129, 3, I1[:1], None, 0, 0)]          # one row, a third column tile of one column
+        outs = [hk.array(np.full((ldo, nc), SENTINEL)) for (nr, nc, ldo, *_) in probs]
+        descs = [K.KevalDesc(dI.ptr if ri is not None else None, dJ.ptr if ci is not None else None, o.ptr, nr, nc, ldo, r0, c0)
+                 for (nr, nc, ldo, ri, ci, r0, c0), o in zip(probs, outs)]
+        arr = (K.KevalDesc * len(descs))(*descs)
+        hk.check(hk.lib.hssk_kernel_eval_vbatched(hk.ctx, C.byref(spec), arr, len(descs)))
         hk.sync()
-        assert np.allclose(o1.get()[:70], kernel_np(X, I1, J1, ktype, 1.3, 3.11, p), rtol=1e-12, atol=1e-14)
-        assert np.allclose(o2.get(), kernel_np(X, np.arange(100, 165), np.arange(120, 160), ktype, 1.3, 3.11, p), rtol=1e-12, atol=1e-14)
+        frac = 0.0
+        for (nr, nc, ldo, ri, ci, r0, c0), o in zip(probs, outs):
+            rr = ri if ri is not None else np.arange(r0, r0 + nr)
+            cc = ci if ci is not None else np.arange(c0, c0 + nc)
+            got = o.get()
+            assert np.array_equal(got[nr:].view(np.uint64), np.full((ldo - nr, nc), SENTINEL).view(np.uint64)), \
+                "kernel_eval type %d p %d d %d: wrote into the padding rows of a %d x %d block" % (ktype, p, d, nr, nc)
+            k, a, A = kernel_ref(X, rr, cc, ktype, h, lam, p)
+            err = np.abs(got[:nr].astype(np.longdouble) - k)
+            bound = kernel_entry_bound(a, A, ktype, d, lam, p)
+            frac = max(frac, float((err / bound).max()))
+            assert np.all(err <= bound), "kernel_eval type %d p %d d %d (%d x %d): %d entries beyond the bound (worst %.3g x)" % (
+                ktype, p, d, nr, nc, int((err > bound).sum()), float((err / bound).max()))
+            if widths is None:
+                assert np.allclose(got[:nr], kernel_np(X, rr, cc, ktype, h, lam, p), rtol=1e-12, atol=1e-14)
+        print("kernel_eval type=%d p=%d d=%d n=%d: largest error / bound %.3f" % (ktype, p, d, n, frac))
+        worst = max(worst, frac)
+    return worst
+
+
+def anova_degrees(d):
+    return sorted({1, min(2, d), min(8, d)})
+
+
+KERNEL_DIMS = (1, 8, 31, 32, 33, 64)      # one pass of 32 staged coordinates, its edges, two passes, the largest dimension
+
+
+def case_kernel_eval_dims(hk, d, n=200):
+    return case_kernel_eval(hk, n=n, d=d, seed=200 + d, kinds=[(0, 1), (1, 1)] + [(2, p) for p in anova_degrees(d)],
+                            widths=kernel_widths(d))
 
 
 def case_knn(hk, n=500, d=8, k=10, seed=22, lattice=False):
@@ -710,17 +874,156 @@ def case_knn(hk, n=500, d=8, k=10, seed=22, lattice=False):
             assert set(mine.tolist()) == set(order[:kk].tolist())
 
 
-def case_kernel_predict(hk, n=257, m=70, d=5, seed=23):
+# heap search (n, d, k): the 64- and 32-coordinate instantiations at a dimension that fills them / leaves them nearly empty, d = 1
+KNN_HEAP_DIMS = ((150, 64, 10), (150, 33, 10), (150, 1, 10))
+# filtered search (n, d, k) with HSSK_KNN_FILTER_MIN=600: both sides of its padded-dimension variants (3|4, 9|10, 17|18) and of
+# its limits d <= 29 and k <= 128 (beyond them, and with n <= 4 k, the heap search answers)
+KNN_FILTER_EDGES = tuple((700, d, 8) for d in (1, 3, 4, 9, 10, 17, 18, 29, 30)) + ((700, 8, 128), (700, 8, 129), (640, 8, 160))
+
+
+def case_knn_filter_edges(hk):
+    import os
+    os.environ["HSSK_KNN_FILTER_MIN"] = "600"
+    try:
+        for (n, d, k) in KNN_FILTER_EDGES:
+            case_knn(hk, n=n, d=d, k=k, seed=700 + d + k)
+    finally:
+        os.environ.pop("HSSK_KNN_FILTER_MIN")
+
+
+# (n, d, leaf): the device clustering keeps a centre of 64 and extents of 2 x 64 coordinates per cluster
+CLUSTER_DIMS = ((3001, 1, 64), (2500, 2, 100), (2000, 33, 64), (1500, 64, 50), (6000, 17, 128))
+
+
+def case_clustering_dims(KM, lib, algo):
+    """Device clustering against the host form at the dimensions' edges, with the splits of large clusters by several workgroups
+    at their default size, never (0) and from 1000 points on: status 0, permutation, points and leaf sizes equal."""
+    import os
+    r = np.random.default_rng(5)
+    for (n, d, leaf) in CLUSTER_DIMS:
+        pts = r.standard_normal((n, d))
+        Xh, ph, lh = KM.clustering(lib, pts, algo, leaf)
+        for wide in (None, "0", "1000"):
+            if wide is not None:
+                os.environ["HSSK_CLUSTER_WIDE_MIN"] = wide
+            try:
+                st, Xp, perm, leaves = KM.clustering_device(lib, pts, algo, leaf)
+            finally:
+                os.environ.pop("HSSK_CLUSTER_WIDE_MIN", None)
+            assert st == 0, (algo, n, d, leaf, wide, st)
+            assert np.array_equal(perm, ph) and np.array_equal(Xp, Xh) and leaves.tolist() == lh.tolist(), (algo, n, d, leaf, wide)
+
+
+def gram_blocks_child(lib_expr, tmp_path=None):
+    """Every batch of GRAM_BATCHES through hssk_gram_vbatched in a fresh process with HSSK_GRAM_BLOCKS=1 (read once per process):
+    the 128 x 128 block kernel for all of them.  lib_expr: python source of the library path in the child.  Returns its output."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = (
+        "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "import kernel_cases as KC\n"
+        "from strumpack_amd import hssk as K\n"
+        "%s\n"
+        "hk = K.Hssk(path)\n"
+        "for mmax, batch in sorted(KC.GRAM_BATCHES.items()):\n"
+        "    KC.case_gram_pchol_id(hk, batch, seed=800 + mmax)\n"
+        "hk.close(); print('gram blocks ok')\n"
+    ) % (here, os.path.dirname(here), lib_expr)
+    res = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, HSSK_GRAM_BLOCKS="1"), capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-3000:])
+    assert res.stdout.strip().endswith("gram blocks ok")
+    return res.stdout
+
+
+def front_end_two_forms(lib_expr, kern, dim, deg, clus, n, leaf, tmp_path, rtol=1e-3, lam=2.5):
+    """n standard normal points in R^dim through the kernel-matrix front end (device clustering, filtered neighbour search, row
+    ID from Gram matrices) and, in a second process, through the forms it replaced (STRUMPACK_AMD_CLUSTER_HOST=1
+    HSSK_KNN_FILTER=0 STRUMPACK_AMD_ID_GRAM=0): the same permutation and tree, the points in that order, ULV residual against
+    the compressed matrix <= 1e-10.  The error of H b on 32 sampled rows against exact np.longdouble kernel rows is limited by
+    the column sample (64 neighbours per point), not by rel_tol, so it is measured for the replaced forms in the same call:
+    err_new <= max(2 err_old, 10 rel_tol), the factor 2 for ranks that come out one off.  Both are printed
+    (profiles/kernelmat_dims.md has the measured ones).  lib_expr: python source of the library path in the child processes."""
+    import os
+    import subprocess
+    import sys
+    kt = {"Gauss": 0, "Laplace": 1, "ANOVA": 2}[kern]
+    h = float(kernel_widths(dim)[kt])
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = (
+        "import sys, numpy as np; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "from strumpack_amd import capi, dist as sdist\n"
+        "%s\n"
+        "L = capi.load(path); n, d = %d, %d\n"
+        "X = np.random.default_rng(78).standard_normal((n, d))\n"
+        "o = capi.StructuredMatrix.options(L, rel_tol=%g, abs_tol=1e-10, leaf_size=%d, max_rank=50000)\n"
+        "H, Xp, perm = sdist.from_kernel(L, X, o, kernel=%r, h=%r, lam=%r, degree=%d, clustering=%r, neighbors=64)\n"
+        "b = np.linspace(-1, 1, n); y = H.mult(b)[:, 0]; H.factor(); x = H.solve(b)[:, 0]\n"
+        "res = float(np.linalg.norm(H.mult(x)[:, 0] - b) / np.linalg.norm(b))\n"
+        "np.savez(sys.argv[1], perm=perm, info=H.node_info(), y=y, Xp=Xp, X=X, res=res, rank=H.rank())\n"
+    ) % (here, os.path.dirname(here), lib_expr, n, dim, rtol, leaf, kern, h, lam, deg, clus)
+    out = []
+    for mode, env in (("new", {}), ("old", {"STRUMPACK_AMD_CLUSTER_HOST": "1", "HSSK_KNN_FILTER": "0", "STRUMPACK_AMD_ID_GRAM": "0"})):
+        f = str(tmp_path / ("dims_%s.npz" % mode))
+        r = subprocess.run([sys.executable, "-c", code, f], env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out.append(np.load(f))
+    new, old = out
+    assert np.array_equal(new["perm"], old["perm"]), "device clustering differs from the host form"
+    assert np.array_equal(new["info"][:, [0, 1, 5]], old["info"][:, [0, 1, 5]]), "tree"
+    for z in (new, old):
+        assert sorted(z["perm"].tolist()) == list(range(1, n + 1)) and np.array_equal(z["Xp"], z["X"][z["perm"] - 1])
+    assert float(new["res"]) <= 1e-10 and float(old["res"]) <= 1e-10, (float(new["res"]), float(old["res"]))
+    I = np.random.default_rng(3).integers(0, n, 32)
+    KI = kernel_ref(new["Xp"], I, np.arange(n), kt, h, lam, deg)[0]
+    ref = KI @ np.linspace(-1, 1, n).astype(np.longdouble)
+    en, eo = (float(np.linalg.norm(z["y"][I] - ref) / np.linalg.norm(ref)) for z in (new, old))
+    print("front end %s d=%d p=%d n=%d: rank new %d old %d, sampled-row error new %.3e old %.3e, ULV residual new %.1e old %.1e" %
+          (kern, dim, deg, n, int(new["rank"]), int(old["rank"]), en, eo, float(new["res"]), float(old["res"])))
+    assert en <= max(2 * eo, 10 * rtol), (en, eo)
+    return en, eo
+
+
+def case_kernel_predict(hk, n=257, m=70, d=5, seed=23, kinds=((0, 1), (1, 1), (2, 2)), widths=None):
+    """hssk_kernel_predict (FP64) against the np.longdouble sum under
+        sum_r |w_r| (kernel_entry_bound of k_rc) + n u sum_r |w_r k_rc|        (n additions of the products, in any order).
+    widths: as in case_kernel_eval (None: 0.9, and the flat tolerance of the first version on top).  Returns error / bound."""
     r = rng(seed)
     X, T, w = r.standard_normal((n, d)), r.standard_normal((m, d)), r.standard_normal(n)
-    dX, dT, dw, dp = hk.array(X.T), hk.array(T.T), hk.array(w), hk.empty((m,))
-    for (ktype, p) in [(0, 1), (1, 1), (2, 2)]:
-        spec = K.KernelSpec(dX.ptr, n, d, ktype, p, 0.9, 2.0)
+    dX, dT, dw = hk.array(X.T), hk.array(T.T), hk.array(w)
+    Z = np.vstack([X, T])
+    worst = 0.0
+    for (ktype, p) in kinds:
+        h = 0.9 if widths is None else float(widths[ktype])
+        dp = hk.array(np.full((m + 2,), SENTINEL))
+        spec = K.KernelSpec(dX.ptr, n, d, ktype, p, h, 2.0)
         hk.check(hk.lib.hssk_kernel_predict(hk.ctx, C.byref(spec), dw.ptr, dT.ptr, m, dp.ptr))
         hk.sync()
-        Z = np.vstack([X, T])
-        Kx = kernel_np(Z, np.arange(n), n + np.arange(m), ktype, 0.9, 0.0, p)
-        assert np.allclose(dp.get(), w @ Kx, rtol=1e-11, atol=1e-12)
+        got = dp.get()
+        assert np.all(got[m:] == SENTINEL), "kernel_predict wrote behind its m predictions"
+        k, a, A = kernel_ref(Z, np.arange(n), n + np.arange(m), ktype, h, 0.0, p)
+        aw = np.abs(w).astype(np.longdouble)
+        ref = w.astype(np.longdouble) @ k
+        bound = aw @ kernel_entry_bound(a, A, ktype, d, 0.0, p) + n * U53 * (aw @ np.abs(k))
+        err = np.abs(got[:m].astype(np.longdouble) - ref)
+        frac = float((err / bound).max())
+        print("kernel_predict type=%d p=%d n=%d m=%d d=%d: largest error / bound %.3f" % (ktype, p, n, m, d, frac))
+        assert np.all(err <= bound), "kernel_predict type %d p %d (n, m, d) = %s: %d predictions beyond the bound (worst %.3g x)" % (
+            ktype, p, (n, m, d), int((err > bound).sum()), frac)
+        if widths is None:
+            assert np.allclose(got[:m], w @ kernel_np(Z, np.arange(n), n + np.arange(m), ktype, h, 0.0, p), rtol=1e-11, atol=1e-12)
+        worst = max(worst, frac)
+    return worst
+
+
+# (n, m, d): one point, n and m on both sides of the 64 training points / 64 test points of a pass and a workgroup, the LDS row
+# stride at its largest dimension, two staging passes' worth of coordinates, and the shape of the first version of the case
+PREDICT_SHAPES = ((1, 1, 1), (63, 64, 33), (64, 65, 64), (65, 1, 32), (257, 70, 5))
+
+
+def case_kernel_predict_dims(hk, n, m, d):
+    return case_kernel_predict(hk, n=n, m=m, d=d, seed=300 + d, kinds=((0, 1), (1, 1), (2, min(8, d))), widths=kernel_widths(d))
 
 
 def case_gather_combine(hk, shapes, seed=31):

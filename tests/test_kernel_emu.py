@@ -160,6 +160,13 @@ def test_clustering_device_form(lib, algo):
             assert np.array_equal(perm, ph) and np.array_equal(Xp, Xh)
 
 
+@pytest.mark.parametrize("algo", ["cobble", "kdtree"])
+def test_clustering_device_form_dims(lib, algo):
+    """d = 1, 2, 17, 33 and 64 (the kernels keep 64 centre and 128 extent coordinates per cluster), every form of the wide split"""
+    import kernel_cases as KC
+    KC.case_clustering_dims(KM, lib, algo)
+
+
 @pytest.mark.parametrize("algo", ["cobble", "kdtree", "pca"])
 def test_median_split_fast_selection_is_the_reference_selection(algo):
     """The median splits select on a copy of the keys and make the reference's nth_element call only when equal keys straddle

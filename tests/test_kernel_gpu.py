@@ -89,6 +89,13 @@ def test_clustering_device_form_is_the_host_form(lib, algo):
     assert st > 0 and np.array_equal(Xp, lat)
 
 
+@pytest.mark.parametrize("algo", ["cobble", "kdtree"])
+def test_clustering_device_form_dims(lib, algo):
+    """d = 1, 2, 17, 33 and 64 (the kernels keep 64 centre and 128 extent coordinates per cluster), every form of the wide split"""
+    import kernel_cases as KC
+    KC.case_clustering_dims(KM, lib, algo)
+
+
 def test_tsqr_staircase_matches_dense_sweep():
     """The TSQR pre-reduction of tall ID panels stacks R factors with interleaved rows and factors only the staircase
     (hssk_qr_desc.stair); the dense sweep of the same stack (STRUMPACK_AMD_TSQR_DENSE=1) must give the same matrix."""
@@ -155,6 +162,21 @@ def test_round6_front_end_against_the_forms_it_replaced(kern, h, dim, clus, rtol
     b = np.linspace(-1, 1, n)
     err = np.linalg.norm(new["y"][I] - KI @ b) / np.linalg.norm(KI @ b)
     assert err <= 1e2 * rtol, err
+
+
+# (kernel, d, ANOVA degree, clustering): d = 1; 16 | 17, where the panels of the row ID stop being evaluated inside the Gram product
+# (hssk_gram_gen_supported) and are written by hssk_kernel_eval_vbatched; 29 | 30, the last dimension of the filtered neighbour
+# search and the first one of the heap search; ANOVA at its largest degree; the largest dimension
+FRONT_END_DIMS = [("Gauss", 1, 1, "cobble"), ("Gauss", 16, 1, "cobble"), ("Gauss", 17, 1, "cobble"), ("Laplace", 29, 1, "kdtree"),
+                  ("Gauss", 30, 1, "cobble"), ("ANOVA", 12, 8, "cobble"), ("Laplace", 64, 1, "kdtree")]
+
+
+@pytest.mark.parametrize("kern,dim,deg,clus", FRONT_END_DIMS)
+def test_front_end_at_the_dimension_switches(kern, dim, deg, clus, tmp_path):
+    """12000 points (above the 8192 from which the device clusters and the filtered search answers) through the front end and,
+    in a second process, through the forms it replaced: kernel_cases.front_end_two_forms."""
+    import kernel_cases as KC
+    KC.front_end_two_forms("from strumpack_amd import _loader; path = _loader.lib_path()", kern, dim, deg, clus, 12000, 128, tmp_path)
 
 
 def test_full_size_properties_100k():

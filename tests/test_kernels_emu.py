@@ -175,12 +175,44 @@ def test_kernel_matrix_entries(hk):
     KC.case_kernel_eval(hk, n=200)
 
 
+@pytest.mark.parametrize("d", KC.KERNEL_DIMS)
+def test_kernel_matrix_entries_dims(hk, d):
+    """Gauss, Laplace and ANOVA (degrees 1, 2 and 8) entries on both sides of the 32 coordinates staged per pass, at d = 1 and
+    at the largest dimension, against the np.longdouble reference under the derived bound; padding rows untouched."""
+    KC.case_kernel_eval_dims(hk, d)
+
+
 def test_gram_pchol_id(hk):
     KC.case_gram_pchol_id(hk, [(300, 40, 1e-3, 1e-12, 1000, 12, 1), (700, 70, 1e-2, 1e-10, 1000, None, 3), (520, 33, 1e-4, 1e-12, 5, 9, 2), (260, 130, 1e-8, 1e-14, 1000, None, 1)])
 
 
+@pytest.mark.parametrize("mmax", sorted(KC.GRAM_BATCHES))
+def test_gram_tile_variants(hk, mmax):
+    """gram_panel_kernel<5 | 12 | 17>: separate batches whose widest panel is 96, 128 | 129, 208 | 209, 256 columns (the
+    dispatch boundaries), and odd row counts in chunks of 37 and of 2 - 3 rows."""
+    KC.case_gram_pchol_id(hk, KC.GRAM_BATCHES[mmax], seed=800 + mmax)
+
+
+def test_gram_block_form_in_a_child_process():
+    """gram_kernel (128 x 128 blocks, HSSK_GRAM_BLOCKS=1) on the same batches"""
+    print(KC.gram_blocks_child('import emu_lib; path = emu_lib.build()'))
+
+
 def test_gram_gen(hk):
     KC.case_gram_gen(hk)
+
+
+@pytest.mark.parametrize("mmax", sorted(KC.GRAM_GEN_BATCHES))
+def test_gram_gen_tile_variants(hk, mmax):
+    """gram_gen_panel_kernel<5 | 12 | 17> on both sides of 128 | 129 and 208 | 209 columns and at 256, a one-column panel
+    next to the widest one, 1 .. 500 rows"""
+    KC.case_gram_gen_batch(hk, mmax)
+
+
+@pytest.mark.parametrize("d", KC.GRAM_GEN_DIMS)
+def test_gram_gen_dims(hk, d):
+    """d = 1, 15 and 16 (the last dimension the fused kernel takes: all 256 fetching threads busy), rows 1 .. 500"""
+    KC.case_gram_gen_dims(hk, d)
 
 
 def test_knn_filtered(hk):
@@ -205,8 +237,26 @@ def test_knn(hk):
     KC.case_knn(hk, n=300, d=4, k=70, seed=26, lattice=True)   # exact ties, duplicates, two pages
 
 
+def test_knn_dims(hk):
+    """the heap search at d = 64 and 33 (knn_kernel<64, ..>, full and half empty) and d = 1 (knn_kernel<8, ..>)"""
+    for (n, d, k) in KC.KNN_HEAP_DIMS:
+        KC.case_knn(hk, n=n, d=d, k=k, seed=30 + d)
+
+
+def test_knn_filtered_edges(hk):
+    """the filtered search (knn2_scan_kernel<3 | 6 | 10 | 16, ..>) on both sides of d = 3 | 4, 9 | 10, 17 | 18 and of its limits (d = 29 | 30,
+    k = 128 | 129, n <= 4 k): beyond them the heap search answers -- the same checks either way"""
+    KC.case_knn_filter_edges(hk)
+
+
 def test_kernel_predict(hk):
     KC.case_kernel_predict(hk)
+
+
+@pytest.mark.parametrize("n,m,d", KC.PREDICT_SHAPES)
+def test_kernel_predict_dims(hk, n, m, d):
+    """FP64 prediction, all three kernels (ANOVA at degree min(8, d)): n and m at 1, 63 .. 65, d = 1, 32, 33, 64"""
+    KC.case_kernel_predict_dims(hk, n, m, d)
 
 
 def test_qr_staircase(hk):
