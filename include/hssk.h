@@ -245,8 +245,13 @@ int hssk_kernel_eval_vbatched(hssk_ctx* ctx, const hssk_kernel_spec* spec, const
 /* exact k nearest neighbours (Euclidean, the point itself excluded) of the points q0 <= i < q1 among all n points:
  * out_idx is k x n (device ints, neighbours of point i in column i, unordered, -1 where n - 1 < k; only the columns
  * of the query range are written -- one process per GPU searches for its own points).  Serves the neighbour lists of
- * HSSMatrix::compress_with_coordinates (HSS/HSSMatrix.compress_kernel.hpp:58-66).  d <= 64. */
+ * HSSMatrix::compress_with_coordinates (HSS/HSSMatrix.compress_kernel.hpp:58-66).  Any d >= 1, no compile-time maximum: up to 64
+ * coordinates a query sits in registers; beyond 64 the coordinates pass through the LDS 32 at a time (same keys, same result).
+ * Large sets (n >= 8192, k <= 128) of d <= 29 or d >= 65 take the filtered search, whose scratch is 4 (d + 18) n bytes beside the
+ * lists (at most 2 GiB at d >= 65: larger sets take the heap kernels).  Point offsets are size_t(i) * d. */
 int hssk_knn(hssk_ctx* ctx, const double* X, int d, int n, int k, int q0, int q1, int* out_idx);
+/* calls of hssk_knn on this context that the filtered search (FP32 matrix cores) answered; the others took the heap kernels */
+long long hssk_knn_filtered_count(hssk_ctx* ctx);
 /* Column sets of the kernel-matrix compression (the sorted, duplicate-free ids a node samples its rows on:
  * HSS/HSSMatrix.compress_kernel.hpp:108-131 for a leaf -- the neighbours of its points outside the leaf --, :159-183 for an
  * inner node -- the union of its children's sets without the ids inside the node).  out = sorted unique ids of
@@ -275,7 +280,8 @@ long long hssk_colsets_max_universe(void);   /* largest universe hssk_colsets ta
  * farthest point or a long displacement chain were met -- X and perm are then NOT to be used and the caller takes the host form
  * (host/Clustering.hpp).  Returns 2 for an algorithm / dimension this form does not take.  Synchronises. */
 int hssk_cluster_median(hssk_ctx* ctx, double* X, int d, int n, int algo, int cluster_size, int* perm, int* status);
-/* pred[c] = sum_r w[r] k(x_r, t_c), c < m; T is d x m (device)   (Kernel::predict, kernel/KernelRegression.hpp:112-123) */
+/* pred[c] = sum_r w[r] k(x_r, t_c), c < m; T is d x m (device)   (Kernel::predict, kernel/KernelRegression.hpp:112-123).
+ * Any d >= 1: beyond 64 coordinates the points pass through the LDS 32 coordinates at a time, same arithmetic per pair. */
 int hssk_kernel_predict(hssk_ctx* ctx, const hssk_kernel_spec* spec, const double* w, const double* T, int m, double* pred);
 /* The promise of the single-precision prediction's matrix-core route: the worst relative error the norm expansion
  * |x|^2 + |t|^2 - 2 x.t can add to a term w_r k(x_r, t_c).  A (training tile, test tile) pair whose scaled norms would exceed it,
@@ -288,7 +294,12 @@ int hssk_kernel_predict(hssk_ctx* ctx, const hssk_kernel_spec* spec, const doubl
  * [5] of the prep and reduce launches. */
 int hssk_kernel_predict_f32(hssk_ctx* ctx, const float* X, long long n, int d, int type, int p, double h,
                             const float* w, const float* T, int m, float* pred, long long* stats);
-/* splits of the training set hssk_kernel_predict_f32 takes for n training and m test points: a function of (n, m) alone */
+/* The same sum for d >= 65 (no upper limit on d; d <= 64 is refused: hssk_kernel_predict_f32 takes it).  Same arguments, grid,
+ * sums and statistics; every tile goes the difference form, the coordinates through the LDS 64 at a time, so stats[0] == 0: at
+ * d >= 65 the route rule above admits only tiles whose exponents are below ~7. */
+int hssk_kernel_predict_f32_wide(hssk_ctx* ctx, const float* X, long long n, int d, int type, int p, double h,
+                                 const float* w, const float* T, int m, float* pred, long long* stats);
+/* splits of the training set hssk_kernel_predict_f32 (and _wide) takes for n training and m test points: a function of (n, m) alone */
 int hssk_kernel_predict_splits(long long n, int m);
 
 /* ---- gathers / scatters ----------------------------------------------------------------------- */

@@ -256,7 +256,9 @@ void Kernel<float>::run_predict(int m, const float* test_host, int ldt, const fl
   float* dp = out_dev;
   if (!dp) { pbuf.reset(new PoolBuf(R.ctx, sizeof(float) * m)); dp = (float*)pbuf->p; }
   long long st[6];
-  ckk(hssk_kernel_predict_f32(R.ctx, R.dX, (long long)nn, (int)dd, device_type(), degree(), (double)width(), dw, dT, m, dp, st));
+  // (beyond 64 coordinates: the entry whose points pass through the LDS in chunks)
+  ckk((dd <= 64 ? hssk_kernel_predict_f32 : hssk_kernel_predict_f32_wide)(R.ctx, R.dX, (long long)nn, (int)dd, device_type(), degree(),
+                                                                          (double)width(), dw, dT, m, dp, st));
   if (out_host) ckk(hssk_memcpy_d2h(R.ctx, out_host, dp, (long long)(sizeof(float) * m)));
   ckk(hssk_sync(R.ctx));
   pstats_[0] = st[0]; pstats_[1] = st[1]; pstats_[2] = st[2]; pstats_[3] = st[3]; pstats_[4] = uploaded; pstats_[5] = resident ? 1 : 0;

@@ -76,6 +76,7 @@ struct hssk_ctx {
   bool watch_open[8] = {false, false, false, false, false, false, false, false};
   size_t sweep_cap = size_t(1) << 20;
   size_t scratch_bytes = 0;
+  long long knn_filtered = 0;   // calls of hssk_knn the filtered search answered (hssk_knn_filtered_count)
 
   // copies `bytes` of host data into the ring and returns the device address (valid for kernels
   // enqueued on `stream` after this call)

@@ -319,6 +319,90 @@ __global__ __launch_bounds__(Q) void knn_kernel(const double* __restrict__ X, in
   if (ub && part == 0) ub[q] = worst;
 }
 
+// The general form beyond KNN_DMAX coordinates: the heap kernel's keys and pages, a query per lane, but neither the query nor the
+// candidates are held whole anywhere -- a point of R^784 is 6 KB.  A tile of KW_CT candidates is met in passes of KW_DC
+// coordinates: the pass of the 64 queries and of the candidates is staged in the LDS, the KW_CT squared distances of a lane carry
+// across the passes in registers (FP64, coordinates in order: the keys are the heap kernel's bit for bit), and after the last pass
+// the keys go through the LDS (over the queries' pass, which is spent) into the lane's heap.  The queries' pass is staged again
+// for every candidate tile: 3 staged values per 32 squared differences.  Throughput is secondary here; the pages and ties are not.
+constexpr int KW_Q = 64;     // queries per workgroup
+constexpr int KW_CT = 32;    // candidates per tile
+constexpr int KW_DC = 32;    // coordinates per pass
+__global__ __launch_bounds__(KW_Q) void knn_wide_kernel(const double* __restrict__ X, int d, int n, int q0, int q1, int kpage,
+                                                        const knn_key_t* __restrict__ lb, int* __restrict__ out_idx, int ldo,
+                                                        knn_key_t* __restrict__ ub) {
+  static_assert(KW_CT * KW_Q <= KW_Q * (KW_DC + 1), "the keys of a tile take the place of the queries' pass");
+  HSSK_SHARED knn_key_t hh[KNN_P * KW_Q];
+  HSSK_SHARED double xq[KW_Q * (KW_DC + 1)];   // [query][coordinate of the pass]; after the last pass: [candidate][query] keys
+  HSSK_SHARED double xc[KW_CT * KW_DC];        // [candidate][coordinate of the pass]: read as broadcasts
+  const int tid = threadIdx.x, qb = q0 + blockIdx.x * KW_Q, q = qb + tid;
+  const bool live = q < q1;
+  for (int s = 0; s < kpage; s++) hh[s * KW_Q + tid] = KNN_EMPTY;
+  const knn_key_t lo = (lb && live) ? lb[q] + 1 : 0;
+  knn_key_t worst = live ? KNN_EMPTY : 0;
+  auto insert = [&](knn_key_t K) {   // (as in knn_kernel: the root replaced, sifted down)
+    int pos = 0;
+    for (;;) {
+      const int l = 2 * pos + 1, r = l + 1;
+      if (l >= kpage) break;
+      knn_key_t kc = hh[l * KW_Q + tid];
+      int c = l;
+      if (r < kpage) {
+        const knn_key_t kr = hh[r * KW_Q + tid];
+        if (kr > kc) { kc = kr; c = r; }
+      }
+      if (kc <= K) break;
+      hh[pos * KW_Q + tid] = kc;
+      pos = c;
+    }
+    hh[pos * KW_Q + tid] = K;
+    worst = hh[tid];
+  };
+  knn_key_t* keys = (knn_key_t*)xq;
+  for (int c0 = 0; c0 < n; c0 += KW_CT) {
+    double s2[KW_CT];
+#pragma unroll
+    for (int u = 0; u < KW_CT; u++) s2[u] = 0.;
+    for (int d0 = 0; d0 < d; d0 += KW_DC) {
+      const int dc = min(KW_DC, d - d0);
+      __syncthreads();
+      // (queries past the range and candidates past the point set read the last one: their keys are never used)
+      for (int e = tid; e < KW_Q * dc; e += KW_Q) {
+        const int pt = e / dc, j = e % dc;
+        xq[pt * (KW_DC + 1) + j] = hssk_gload(X, (size_t)min(qb + pt, q1 - 1) * d + d0 + j);
+      }
+      for (int e = tid; e < KW_CT * dc; e += KW_Q) {
+        const int pt = e / dc, j = e % dc;
+        xc[pt * KW_DC + j] = hssk_gload(X, (size_t)min(c0 + pt, n - 1) * d + d0 + j);
+      }
+      __syncthreads();
+      for (int j = 0; j < dc; j++) {
+        const double x = xq[tid * (KW_DC + 1) + j];
+#pragma unroll
+        for (int u = 0; u < KW_CT; u++) {
+          const double df = x - xc[u * KW_DC + j];
+          s2[u] += df * df;
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < KW_CT; u++) keys[u * KW_Q + tid] = knn_pack((float)s2[u], c0 + u);
+    const int cend = min(KW_CT, n - c0);
+    for (int u = 0; u < cend; u++) {
+      const knn_key_t K = keys[u * KW_Q + tid];
+      if (K >= lo && K < worst && c0 + u != q) insert(K);
+    }
+  }
+  if (!live) return;
+  if (out_idx)
+    for (int s = 0; s < kpage; s++) {
+      const knn_key_t K = hh[s * KW_Q + tid];
+      out_idx[(size_t)q * ldo + s] = K == KNN_EMPTY ? -1 : (int)(K & 0xffffffffu);
+    }
+  if (ub) ub[q] = worst;
+}
+
 // prediction[c] = sum_r w[r] k(x_r, t_c)   (no lambda: train and test points are different sets)
 constexpr int PR_T = 64;
 __global__ __launch_bounds__(PR_T) void kernel_predict_kernel(hssk_kernel_spec ks, const double* __restrict__ w,
@@ -370,6 +454,94 @@ __global__ __launch_bounds__(PR_T) void kernel_predict_kernel(hssk_kernel_spec k
     }
   }
   if (live) pred[c] = sum;
+}
+
+// e_E = (1 / E) sum_q (-1)^(q + 1) e_(E - q) s_q for E = 1 .. p, the sums in kernel_predict_kernel's order (every index a
+// constant: the arrays stay in registers)
+template <int E>
+__device__ inline void anova_newton(const double (&S)[8], double (&K)[9], int p, double& v) {
+  anova_newton<E - 1>(S, K, p, v);
+  if (E <= p) {
+    double s = 0.;
+#pragma unroll
+    for (int q = 1; q <= E; q++) s += ((q & 1) ? 1. : -1.) * K[E - q] * S[q - 1];
+    K[E] = s / E;
+    v = K[E];
+  }
+}
+template <>
+__device__ inline void anova_newton<0>(const double (&)[8], double (&K)[9], int, double&) { K[0] = 1.; }
+
+// The same sum beyond KNN_DMAX coordinates: whole points no longer fit the LDS, so a tile of RT training points meets the
+// workgroup's 64 test points in passes of KE_DC coordinates.  What a pair has accumulated -- the distance (Gauss, Laplace) or the
+// p power sums of its per-coordinate exponentials (ANOVA) -- carries across the passes in registers; RT is what the registers
+// hold (32 distances, 8 x 8 power sums).  Per pair the coordinates are met in order and the pairs of a test point in training
+// order, as in kernel_predict_kernel: the same arithmetic, the same error bound.  The test points' pass is staged again for
+// every training tile (one staged value per RT differences).
+template <int TYPE, int RT>
+__global__ __launch_bounds__(PR_T) void kernel_predict_wide_kernel(hssk_kernel_spec ks, const double* __restrict__ w,
+                                                                   const double* __restrict__ T, int m, double* __restrict__ pred) {
+  constexpr int NS = TYPE == 2 ? 8 : 1;   // sums a pair carries
+  HSSK_SHARED double xt[PR_T * (KE_DC + 1)];   // [test point][coordinate of the pass]
+  HSSK_SHARED double xr[RT * KE_DC];           // [training point][coordinate of the pass]: read as broadcasts
+  HSSK_SHARED double wr[RT];
+  const int tid = threadIdx.x, cb = blockIdx.x * PR_T, c = cb + tid, d = ks.d, P = ks.p;
+  const double h2 = 2. * ks.h * ks.h;
+  double sum = 0.;
+  for (long long r0 = 0; r0 < ks.n; r0 += RT) {
+    double acc[RT][NS];
+#pragma unroll
+    for (int r = 0; r < RT; r++)
+#pragma unroll
+      for (int q = 0; q < NS; q++) acc[r][q] = 0.;
+    for (int d0 = 0; d0 < d; d0 += KE_DC) {
+      const int dc = min(KE_DC, d - d0);
+      __syncthreads();
+      // (test points past m and training points past n read the last one; their results are dropped)
+      for (int e = tid; e < PR_T * dc; e += PR_T) {
+        const int pt = e / dc, j = e % dc;
+        xt[pt * (KE_DC + 1) + j] = hssk_gload(T, (size_t)min(cb + pt, m - 1) * d + d0 + j);
+      }
+      for (int e = tid; e < RT * dc; e += PR_T) {
+        const int pt = e / dc, j = e % dc;
+        xr[pt * KE_DC + j] = hssk_gload(ks.X, (size_t)min(r0 + pt, ks.n - 1) * d + d0 + j);
+      }
+      if (d0 == 0 && tid < RT) wr[tid] = r0 + tid < ks.n ? w[r0 + tid] : 0.;
+      __syncthreads();
+      for (int j = 0; j < dc; j++) {
+        const double t = xt[tid * (KE_DC + 1) + j];
+#pragma unroll
+        for (int r = 0; r < RT; r++) {
+          const double df = xr[r * KE_DC + j] - t;
+          if (TYPE == 2) {
+            const double tmp = exp(-(df * df) / h2);
+            double pw = tmp;
+#pragma unroll
+            for (int q = 0; q < NS; q++)
+              if (q < P) { acc[r][q] += pw; pw *= tmp; }
+          } else {
+            acc[r][0] += TYPE == 0 ? df * df : fabs(df);
+          }
+        }
+      }
+    }
+    const int rend = (int)min((long long)RT, ks.n - r0);
+#pragma unroll
+    for (int r = 0; r < RT; r++)
+      if (r < rend) {
+        double v = 0.;
+        if (TYPE == 2) {
+          double S[8], Kpp[9];
+#pragma unroll
+          for (int q = 0; q < 8; q++) S[q] = acc[r][q < NS ? q : 0];
+          anova_newton<8>(S, Kpp, P, v);
+        } else {
+          v = exp(acc[r][0] * (TYPE == 0 ? -1. / h2 : -1. / ks.h));
+        }
+        sum += wr[r] * v;
+      }
+  }
+  if (c < m) pred[c] = sum;
 }
 
 void check_spec(const hssk_kernel_spec& ks) {
@@ -478,6 +650,10 @@ knn_key_t* knn_exhaustive(hssk_ctx* ctx, const double* X, int d, int n, int k, i
     const knn_key_t* lb = pg ? kb + (size_t)((pg - 1) & 1) * n : nullptr;
     knn_key_t* ub = kb + (size_t)(pg & 1) * n;
     int* oi = out_idx ? out_idx + pg * KNN_P : nullptr;
+    if (d > KNN_DMAX) {   // (no window: the filtered search does not come this way)
+      HSSK_LAUNCH(knn_wide_kernel, dim3((unsigned)((q1 - q0 + KW_Q - 1) / KW_Q)), dim3(KW_Q), 0, ctx->stream, X, d, n, q0, q1, kp, lb, oi, k, ub);
+      continue;
+    }
     // (queries per workgroup: threads / lanes per query)
     static const bool lq1 = [] { const char* e = std::getenv("HSSK_KNN_LQ"); return e && e[0] == '1'; }();
     const int nqr = q1 - q0;
@@ -579,13 +755,74 @@ __global__ __launch_bounds__(256) void knn2_prep_kernel(const double* __restrict
   if (tid == 0) nmax[blockIdx.x] = red[0];
 }
 
+// ---- beyond KNN_DMAX coordinates: the same operand without a bound on d.  A thread of the mean kernels meets the coordinates
+// t, t + 256, ... (any d; the reads of a workgroup are contiguous), the mean lies in global memory instead of the LDS, and Cf has
+// KPa rows: -2 (x - mean) | |x - mean|^2 | 1 | zeros up to a whole number of the scan's chunks.  The threshold has no row here: the
+// scan adds it by a k-step of its own.
+__global__ __launch_bounds__(256) void knn2w_mean_kernel(const double* __restrict__ X, int d, int n, double* __restrict__ part) {
+  for (int j = threadIdx.x; j < d; j += 256) {
+    double s = 0.;
+    for (long long i = blockIdx.x; i < n; i += K2_G) s += X[(size_t)i * d + j];
+    part[(size_t)blockIdx.x * d + j] = s;
+  }
+}
+__global__ __launch_bounds__(256) void knn2w_meanfin_kernel(const double* __restrict__ part, int d, int n, double* __restrict__ mean) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= d) return;
+  double a = 0.;
+  for (int g = 0; g < K2_G; g++) a += part[(size_t)g * d + j];
+  mean[j] = a / n;
+}
+__global__ __launch_bounds__(256) void knn2w_prep_kernel(const double* __restrict__ X, int d, int n, int ldc, int KPa,
+                                                         const double* __restrict__ mean, float* __restrict__ Cf, float* __restrict__ nmax) {
+  HSSK_SHARED float red[256];
+  const int tid = threadIdx.x;
+  float big = 0.f;
+  for (long long i = (long long)blockIdx.x * 256 + tid; i < ldc; i += (long long)gridDim.x * 256) {
+    if (i < n) {
+      double s2 = 0.;
+      for (int j = 0; j < d; j++) {
+        const double c = X[(size_t)i * d + j] - mean[j];
+        s2 += c * c;
+        Cf[(size_t)j * ldc + i] = (float)(-2. * c);
+      }
+      const float nf = (float)s2;
+      Cf[(size_t)d * ldc + i] = nf;
+      big = fmaxf(big, nf);
+    } else {
+      for (int j = 0; j < d; j++) Cf[(size_t)j * ldc + i] = 0.f;
+      Cf[(size_t)d * ldc + i] = 3.0e38f;
+    }
+    Cf[(size_t)(d + 1) * ldc + i] = 1.f;   // meets the query's norm
+    for (int j = d + 2; j < KPa; j++) Cf[(size_t)j * ldc + i] = 0.f;
+  }
+  red[tid] = big;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
+    __syncthreads();
+  }
+  if (tid == 0) nmax[blockIdx.x] = red[0];
+}
+
 // KSM k-steps of two coordinates (KP = 2 KSM >= d + 3 rows of Cf), TC candidates per LDS tile.  A wave: queries
 // q0 + 64 w .. + 63 in two groups of 32 (group g, query l & 31; the lane halves l >> 5 supply the two coordinates of a k-step and
 // receive different candidate rows, so each half keeps a list of its own).  Row d + 2 of the product is 1 x (-tau_q): the
 // accumulator IS d2 - tau_q and its sign bit the verdict; a lane shifts the 16 sign bits of a block into one word and appends
 // (block, bits) to its list when any is set -- two instructions per pair and one predicated store per lane, group and block.
+//
+// WIDE (d > KNN_DMAX): the K loop in chunks.  KSM is then the k-steps of a CHUNK (KP = 2 KSM rows of Cf); the accumulators of the
+// tile's TC / 32 blocks x 64 queries stay in registers while chunk after chunk of the candidates' rows passes through the LDS tile
+// and of the queries' side (a query is a point: its coordinates are -Cf / 2, read from Cf) through bq, both fetched a chunk ahead.
+// The k-steps run in the order 0, 1, 2, ... of the rows, exactly as in the unchunked loop -- a chunk boundary reloads operands,
+// it does not split a sum -- and the threshold comes last as one more k-step (1 x -tau_q from the lanes of half 0, zeros from
+// the others).  So the accumulator is the same left-to-right FP32 sum of K' = d + 2 (norms included) + up to KP - 1 zero rows + 2
+// (threshold step) products, and the error bound of the pass test is the one above with K' for K: inputs and norms rounded to
+// FP32, K' accumulations of terms bounded by 2 (|c|^2 + |q|^2), i.e. marg = 2.02 (K' + 6) 2^-23 (|q|^2 + max |c|^2) with
+// K' = KPa + 2 >= the number of products.  The blocks of a tile are listed after its last chunk; a compaction between two of them
+// tightens tau_q for the next tile only (a looser threshold lists more, never less).
 constexpr int K2_CAPH = 128;     // ids a lane half lists between two compactions of its query (and the words that hold them)
-template <int KSM, int TC>
+template <int KSM, int TC, bool WIDE = false>
 __global__ __launch_bounds__(256) void knn2_scan_kernel(const double* __restrict__ X, const float* __restrict__ Cf, int ldc, int d, int n,
                                                         int q0, int q1, int k, const float* __restrict__ nmax,
                                                         unsigned* __restrict__ list, int* __restrict__ kept, int* __restrict__ out_idx, int ldo,
@@ -600,6 +837,9 @@ __global__ __launch_bounds__(256) void knn2_scan_kernel(const double* __restrict
   if (qbase >= q1) return;
   long long dbg_comp = 0, dbg_listed = 0;
   float bq[2][KSM], marg[2];
+  float thr[2] = {1.f, 1.f}, nqv[2] = {0.f, 0.f};   // WIDE: minus the query's threshold (lanes of half 0), its norm
+  bool liveq[2] = {false, false};
+  const int KPa = WIDE ? ((d + 2 + KP - 1) / KP) * KP : KP;   // rows of Cf
   int nw[2] = {0, 0}, nh[2] = {0, 0}, kc[2] = {0, 0};   // words / ids listed since the query's last compaction, ids it kept
   unsigned* seg[2];
   float big = 0.f;
@@ -616,12 +856,16 @@ __global__ __launch_bounds__(256) void knn2_scan_kernel(const double* __restrict
 #pragma unroll
     for (int s = 0; s < KSM; s++) {
       const int kk = 2 * s + half;
-      bq[g][s] = kk == trow ? (live ? -1.0e38f : 1.f)
-                            : (!live ? 0.f : (kk < d ? -0.5f * Cf[(size_t)kk * ldc + q] : (kk == d ? 1.f : (kk == d + 1 ? nq : 0.f))));
+      if (WIDE) bq[g][s] = 0.f;   // (filled chunk by chunk in the scan)
+      else bq[g][s] = kk == trow ? (live ? -1.0e38f : 1.f)
+                                 : (!live ? 0.f : (kk < d ? -0.5f * Cf[(size_t)kk * ldc + q] : (kk == d ? 1.f : (kk == d + 1 ? nq : 0.f))));
     }
+    thr[g] = live ? -1.0e38f : 1.f;
+    nqv[g] = nq;
+    liveq[g] = live;
     // what the FP32 evaluation can be off by: inputs and norms rounded to FP32, K + 2 accumulations of terms bounded by
     // (|c| + |q|)^2 <= 2 (|c|^2 + |q|^2)
-    marg[g] = fmaxf(2.02f * ((float)(KP + 6) * 1.1920929e-7f) * (nq + big), 1.0e-30f);
+    marg[g] = fmaxf(2.02f * ((float)((WIDE ? KPa + 2 : KP) + 6) * 1.1920929e-7f) * (nq + big), 1.0e-30f);
     seg[g] = list + ((size_t)(wid * 64 + 32 * g + l32) * 2 + half) * K2_CAPH;
   }
   // ---- compaction of query j (0 .. 63, uniform) of this wave; fin: the ids go out instead of into the kept list
@@ -715,7 +959,12 @@ __global__ __launch_bounds__(256) void knn2_scan_kernel(const double* __restrict
     if (l32 == j32) {
       if (g) { nw[1] = 0; nh[1] = 0; kc[1] = o; }
       else { nw[0] = 0; nh[0] = 0; kc[0] = o; }
-      if (o >= k && half == (trow & 1)) {
+      if (WIDE) {
+        if (o >= k && half == 0) {
+          const float t = -(kf * (1.f + 4.8e-7f) + (g ? marg[1] : marg[0]));
+          if (g) thr[1] = t; else thr[0] = t;
+        }
+      } else if (o >= k && half == (trow & 1)) {
         const float t = -(kf * (1.f + 4.8e-7f) + (g ? marg[1] : marg[0]));
 #pragma unroll
         for (int s = 0; s < KSM; s++)
@@ -730,47 +979,134 @@ __global__ __launch_bounds__(256) void knn2_scan_kernel(const double* __restrict
     return ((it & 1) ? own + off : own - off + ntile) % ntile;
   };
   hssk_f4 v[NV];
-  auto gfetch = [&](int t) {
+  if constexpr (WIDE) {
+    const int nch = KPa / KP;
+    float bqn[2][KSM];
+    // chunk ch of tile t: the candidates' KP rows and the queries' side of the same rows
+    auto cfetch = [&](int t, int ch) {
 #pragma unroll
-    for (int r = 0; r < NV; r++) {
-      const int e = min(lane + 64 * r, KP * TC / 4 - 1), row = e / (TC / 4), c4 = e % (TC / 4);
-      v[r] = *(const hssk_f4*)(Cf + (size_t)row * ldc + (size_t)t * TC + 4 * c4);
+      for (int r = 0; r < NV; r++) {
+        const int e = min(lane + 64 * r, KP * TC / 4 - 1), row = e / (TC / 4), c4 = e % (TC / 4);
+        v[r] = *(const hssk_f4*)(Cf + (size_t)(ch * KP + row) * ldc + (size_t)t * TC + 4 * c4);
+      }
+#pragma unroll
+      for (int g = 0; g < 2; g++)
+#pragma unroll
+        for (int s = 0; s < KSM; s++) {
+          // (a clamped address and a select instead of a branch per load: Cf has ldc columns and KPa > d rows)
+          const int kk = ch * KP + 2 * s + half;
+          const float nq = g ? nqv[1] : nqv[0];
+          const float x = -0.5f * Cf[(size_t)min(kk, d - 1) * ldc + min(qbase + 32 * g + l32, ldc - 1)];
+          const float b = kk < d ? x : (kk == d ? 1.f : (kk == d + 1 ? nq : 0.f));
+          bqn[g][s] = (g ? liveq[1] : liveq[0]) ? b : 0.f;
+        }
+    };
+    cfetch(tile_of(0), 0);
+#pragma unroll 1
+    for (int it = 0; it < ntile; it++) {
+      const int t = tile_of(it);
+      hssk_f16v acc[TC / 32][2];
+#pragma unroll
+      for (int b = 0; b < TC / 32; b++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) { acc[b][0][r] = 0.f; acc[b][1][r] = 0.f; }
+#pragma unroll 1
+      for (int ch = 0; ch < nch; ch++) {
+        hssk_wave_sync();   // (the tile is this wave's alone: its reads of the previous chunk are issued)
+#pragma unroll
+        for (int r = 0; r < NV; r++)
+          if (lane + 64 * r < KP * TC / 4) *(hssk_f4*)(tile + 4 * (lane + 64 * r)) = v[r];
+#pragma unroll
+        for (int s = 0; s < KSM; s++) { bq[0][s] = bqn[0][s]; bq[1][s] = bqn[1][s]; }
+        hssk_wave_sync();
+        if (ch + 1 < nch) cfetch(t, ch + 1);   // (the next tile's first chunk: after the listing below, whose compactions need the registers)
+#pragma unroll
+        for (int s = 0; s < KSM; s++)
+#pragma unroll
+          for (int b = 0; b < TC / 32; b++) {
+            const float a = tile[(2 * s + half) * TC + b * 32 + l32];
+            acc[b][0] = hssk_mfma_f32_32x32x2(a, bq[0][s], acc[b][0]);
+            acc[b][1] = hssk_mfma_f32_32x32x2(a, bq[1][s], acc[b][1]);
+          }
+      }
+      // the threshold's k-step: 1 x (-tau_q) into every row of the query's column
+      const float one = half == 0 ? 1.f : 0.f, t0 = half == 0 ? thr[0] : 0.f, t1 = half == 0 ? thr[1] : 0.f;
+#pragma unroll
+      for (int b = 0; b < TC / 32; b++) {
+        acc[b][0] = hssk_mfma_f32_32x32x2(one, t0, acc[b][0]);
+        acc[b][1] = hssk_mfma_f32_32x32x2(one, t1, acc[b][1]);
+      }
+      // the verdicts of all blocks first: the accumulators are spent before a compaction runs
+      unsigned mm[TC / 32][2];
+#pragma unroll
+      for (int b = 0; b < TC / 32; b++) {
+        unsigned m0 = 0, m1 = 0;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          m0 = (m0 << 1) | (hssk_fbits(acc[b][0][r]) >> 31);
+          m1 = (m1 << 1) | (hssk_fbits(acc[b][1][r]) >> 31);
+        }
+        mm[b][0] = m0; mm[b][1] = m1;
+      }
+#pragma unroll
+      for (int b = 0; b < TC / 32; b++) {
+        const unsigned m0 = mm[b][0], m1 = mm[b][1];
+        const unsigned blk = (unsigned)(t * (TC / 32) + b) << 16;
+        if (m0) { seg[0][nw[0]] = blk | m0; nw[0]++; nh[0] += __builtin_popcount(m0); }
+        if (m1) { seg[1][nw[1]] = blk | m1; nw[1]++; nh[1] += __builtin_popcount(m1); }
+        for (int g = 0; g < 2; g++) {
+          unsigned long long need = hssk_ballot((g ? nh[1] : nh[0]) > K2_CAPH - 16);
+          while (need) {
+            compact(32 * g + (__builtin_ctzll(need) & 31), false);
+            need = hssk_ballot((g ? nh[1] : nh[0]) > K2_CAPH - 16);
+          }
+        }
+      }
+      if (it + 1 < ntile) cfetch(tile_of(it + 1), 0);
     }
-  };
-  gfetch(tile_of(0));
-  for (int it = 0; it < ntile; it++) {
-    const int t = tile_of(it);
-    hssk_wave_sync();   // (the tile is this wave's alone: its reads of the previous one are issued)
+  } else {
+    auto gfetch = [&](int t) {
 #pragma unroll
-    for (int r = 0; r < NV; r++)
-      if (lane + 64 * r < KP * TC / 4) *(hssk_f4*)(tile + 4 * (lane + 64 * r)) = v[r];
-    hssk_wave_sync();
-    if (it + 1 < ntile) gfetch(tile_of(it + 1));
-    for (int b = 0; b < TC / 32; b++) {
-      hssk_f16v acc0, acc1;
-#pragma unroll
-      for (int r = 0; r < 16; r++) { acc0[r] = 0.f; acc1[r] = 0.f; }
-#pragma unroll
-      for (int s = 0; s < KSM; s++) {
-        const float a = tile[(2 * s + half) * TC + b * 32 + l32];
-        acc0 = hssk_mfma_f32_32x32x2(a, bq[0][s], acc0);
-        acc1 = hssk_mfma_f32_32x32x2(a, bq[1][s], acc1);
+      for (int r = 0; r < NV; r++) {
+        const int e = min(lane + 64 * r, KP * TC / 4 - 1), row = e / (TC / 4), c4 = e % (TC / 4);
+        v[r] = *(const hssk_f4*)(Cf + (size_t)row * ldc + (size_t)t * TC + 4 * c4);
       }
-      unsigned m0 = 0, m1 = 0;
+    };
+    gfetch(tile_of(0));
+    for (int it = 0; it < ntile; it++) {
+      const int t = tile_of(it);
+      hssk_wave_sync();   // (the tile is this wave's alone: its reads of the previous one are issued)
 #pragma unroll
-      for (int r = 0; r < 16; r++) {
-        m0 = (m0 << 1) | (hssk_fbits(acc0[r]) >> 31);
-        m1 = (m1 << 1) | (hssk_fbits(acc1[r]) >> 31);
-      }
-      const unsigned blk = (unsigned)(t * (TC / 32) + b) << 16;
-      if (m0) { seg[0][nw[0]] = blk | m0; nw[0]++; nh[0] += __builtin_popcount(m0); }
-      if (m1) { seg[1][nw[1]] = blk | m1; nw[1]++; nh[1] += __builtin_popcount(m1); }
-      // a lane half lists at most 16 ids per block: compact what could overflow on the next one
-      for (int g = 0; g < 2; g++) {
-        unsigned long long need = hssk_ballot((g ? nh[1] : nh[0]) > K2_CAPH - 16);
-        while (need) {
-          compact(32 * g + (__builtin_ctzll(need) & 31), false);
-          need = hssk_ballot((g ? nh[1] : nh[0]) > K2_CAPH - 16);
+      for (int r = 0; r < NV; r++)
+        if (lane + 64 * r < KP * TC / 4) *(hssk_f4*)(tile + 4 * (lane + 64 * r)) = v[r];
+      hssk_wave_sync();
+      if (it + 1 < ntile) gfetch(tile_of(it + 1));
+      for (int b = 0; b < TC / 32; b++) {
+        hssk_f16v acc0, acc1;
+#pragma unroll
+        for (int r = 0; r < 16; r++) { acc0[r] = 0.f; acc1[r] = 0.f; }
+#pragma unroll
+        for (int s = 0; s < KSM; s++) {
+          const float a = tile[(2 * s + half) * TC + b * 32 + l32];
+          acc0 = hssk_mfma_f32_32x32x2(a, bq[0][s], acc0);
+          acc1 = hssk_mfma_f32_32x32x2(a, bq[1][s], acc1);
+        }
+        unsigned m0 = 0, m1 = 0;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          m0 = (m0 << 1) | (hssk_fbits(acc0[r]) >> 31);
+          m1 = (m1 << 1) | (hssk_fbits(acc1[r]) >> 31);
+        }
+        const unsigned blk = (unsigned)(t * (TC / 32) + b) << 16;
+        if (m0) { seg[0][nw[0]] = blk | m0; nw[0]++; nh[0] += __builtin_popcount(m0); }
+        if (m1) { seg[1][nw[1]] = blk | m1; nw[1]++; nh[1] += __builtin_popcount(m1); }
+        // a lane half lists at most 16 ids per block: compact what could overflow on the next one
+        for (int g = 0; g < 2; g++) {
+          unsigned long long need = hssk_ballot((g ? nh[1] : nh[0]) > K2_CAPH - 16);
+          while (need) {
+            compact(32 * g + (__builtin_ctzll(need) & 31), false);
+            need = hssk_ballot((g ? nh[1] : nh[0]) > K2_CAPH - 16);
+          }
         }
       }
     }
@@ -782,12 +1118,12 @@ __global__ __launch_bounds__(256) void knn2_scan_kernel(const double* __restrict
   }
 }
 
-template <int KSM, int TC>
+template <int KSM, int TC, bool WIDE = false>
 void knn2_launch_scan(hssk_ctx* ctx, int nwaves, const double* X, const float* Cf, int ldc, int d, int n, int q0, int q1, int k,
                       const float* nmax, unsigned* list, int* kept, int* out_idx, long long* dbg) {
   const size_t shm = 4 * (sizeof(float) * (2 * KSM) * TC + sizeof(int) * 512);
-  hssk_rt::allow_dynamic_lds(knn2_scan_kernel<KSM, TC>, shm);
-  HSSK_LAUNCH((knn2_scan_kernel<KSM, TC>), dim3((unsigned)((nwaves + 3) / 4)), dim3(256), shm, ctx->stream, X, Cf, ldc, d, n, q0, q1, k, nmax,
+  hssk_rt::allow_dynamic_lds(knn2_scan_kernel<KSM, TC, WIDE>, shm);
+  HSSK_LAUNCH((knn2_scan_kernel<KSM, TC, WIDE>), dim3((unsigned)((nwaves + 3) / 4)), dim3(256), shm, ctx->stream, X, Cf, ldc, d, n, q0, q1, k, nmax,
               list, kept, out_idx, k, dbg);
 }
 }  // namespace
@@ -796,21 +1132,32 @@ extern "C" int hssk_knn(hssk_ctx* ctx, const double* X, int d, int n, int k, int
   HSSK_API_BEGIN
   if (n <= 0 || k <= 0 || q1 <= q0) return 0;
   if (q0 < 0 || q1 > n) throw std::invalid_argument("hssk_knn: query range outside the point set");
-  if (d <= 0 || d > KNN_DMAX) throw std::invalid_argument("hssk_knn: point dimension must be in [1, 64]");
+  if (d <= 0) throw std::invalid_argument("hssk_knn: point dimension must be positive");
   // the filtered search pays from a few thousand points on (HSSK_KNN_FILTER_MIN; HSSK_KNN_FILTER=0: always the heap kernel);
   // its lists name a candidate by (block of 32, bit): 2^16 blocks
   static const bool filt = [] { const char* e = std::getenv("HSSK_KNN_FILTER"); return !(e && e[0] == '0'); }();
   const char* fmin_env = std::getenv("HSSK_KNN_FILTER_MIN");   // (read per call: the tests take both searches in one process)
   const int fmin_n = fmin_env ? std::atoi(fmin_env) : 8192;
-  if (!filt || n < fmin_n || k > 128 || d > 29 || n <= 4 * k || n > (1 << 21) - 256) {
+  // dimensions: d <= 29 (the rows of Cf in one LDS tile, the queries' side in registers) and d > 64 (the K loop in chunks of
+  // K2W_KSM k-steps: its LDS does not grow with d); between them the heap kernel, whose query sits in registers, answers
+  constexpr int K2W_KSM = 8, K2W_TC = 64;   // (64 candidates: the accumulators of 2 blocks x 64 queries are 64 registers)
+  const bool wide = d > KNN_DMAX;
+  const size_t wide_shm = 4 * (sizeof(float) * (2 * K2W_KSM) * K2W_TC + sizeof(int) * 512);
+  // the operand Cf of the chunked form is 4 (d + 18) n bytes of scratch: beyond 2 GiB (n = 2^19 at d = 1000) the general
+  // form, which needs none, answers instead of an allocation that may fail
+  const bool wide_big = wide && sizeof(float) * ((size_t)d + 18) * ((size_t)n + 127) > (size_t(1) << 31);
+  if (!filt || n < fmin_n || k > 128 || (d > 29 && !wide) || n <= 4 * k || n > (1 << 21) - 256 ||
+      (wide && wide_shm > hssk_rt::max_lds_per_workgroup()) || wide_big) {
     knn_exhaustive(ctx, X, d, n, k, q0, q1, out_idx, 0);
     return 0;
   }
-  const int KSM = d <= 3 ? 3 : (d <= 9 ? 6 : (d <= 17 ? 10 : 16)), KP = 2 * KSM, TC = 128;
+  ctx->knn_filtered++;
+  const int KSM = d <= 3 ? 3 : (d <= 9 ? 6 : (d <= 17 ? 10 : 16)), TC = 128;
+  const int KP = wide ? ((d + 2 + 2 * K2W_KSM - 1) / (2 * K2W_KSM)) * (2 * K2W_KSM) : 2 * KSM;   // rows of Cf
   const int ldc = ((n + TC - 1) / TC) * TC, nq = q1 - q0, nw = (nq + 63) / 64;
   // scratch: Cf | partial means | norms | lists (words) | kept ids
   const size_t o_cf = 0, b_cf = sizeof(float) * (size_t)KP * ldc;
-  const size_t o_pm = (o_cf + b_cf + 255) & ~size_t(255), b_pm = sizeof(double) * K2_G * d;
+  const size_t o_pm = (o_cf + b_cf + 255) & ~size_t(255), b_pm = sizeof(double) * (K2_G + 1) * (size_t)d;   // (+ the mean itself: wide)
   const size_t o_nm = (o_pm + b_pm + 255) & ~size_t(255), b_nm = sizeof(float) * K2_G;
   const size_t o_ls = (o_nm + b_nm + 255) & ~size_t(255), b_ls = sizeof(unsigned) * (size_t)nw * 64 * 2 * K2_CAPH;
   const size_t o_kp = (o_ls + b_ls + 255) & ~size_t(255), b_kp = sizeof(int) * (size_t)nw * 64 * 128;
@@ -827,12 +1174,20 @@ extern "C" int hssk_knn(hssk_ctx* ctx, const double* X, int d, int n, int k, int
     hssk_rt::memset_async(dbg, 0, 32, ctx->stream);
     if (const char* e = std::getenv("HSSK_KNN_DRY")) { long long m = std::atoll(e); hssk_rt::h2d(dbg + 2, &m, 8, ctx->stream); hssk_rt::sync(ctx->stream); }
   }
-  HSSK_LAUNCH(knn2_mean_kernel, dim3(K2_G), dim3(256), 0, ctx->stream, X, d, n, part);
-  HSSK_LAUNCH(knn2_prep_kernel, dim3(K2_G), dim3(256), 0, ctx->stream, X, d, n, ldc, KP, part, Cf, nmax);
-  if (KSM == 3) knn2_launch_scan<3, 128>(ctx, nw, X, Cf, ldc, d, n, q0, q1, k, nmax, list, kept, out_idx, dbg);
-  else if (KSM == 6) knn2_launch_scan<6, 128>(ctx, nw, X, Cf, ldc, d, n, q0, q1, k, nmax, list, kept, out_idx, dbg);
-  else if (KSM == 10) knn2_launch_scan<10, 128>(ctx, nw, X, Cf, ldc, d, n, q0, q1, k, nmax, list, kept, out_idx, dbg);
-  else knn2_launch_scan<16, 128>(ctx, nw, X, Cf, ldc, d, n, q0, q1, k, nmax, list, kept, out_idx, dbg);
+  if (wide) {
+    double* mean = part + (size_t)K2_G * d;
+    HSSK_LAUNCH(knn2w_mean_kernel, dim3(K2_G), dim3(256), 0, ctx->stream, X, d, n, part);
+    HSSK_LAUNCH(knn2w_meanfin_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)part, d, n, mean);
+    HSSK_LAUNCH(knn2w_prep_kernel, dim3(K2_G), dim3(256), 0, ctx->stream, X, d, n, ldc, KP, (const double*)mean, Cf, nmax);
+    knn2_launch_scan<K2W_KSM, K2W_TC, true>(ctx, nw, X, Cf, ldc, d, n, q0, q1, k, nmax, list, kept, out_idx, dbg);
+  } else {
+    HSSK_LAUNCH(knn2_mean_kernel, dim3(K2_G), dim3(256), 0, ctx->stream, X, d, n, part);
+    HSSK_LAUNCH(knn2_prep_kernel, dim3(K2_G), dim3(256), 0, ctx->stream, X, d, n, ldc, KP, part, Cf, nmax);
+    if (KSM == 3) knn2_launch_scan<3, 128>(ctx, nw, X, Cf, ldc, d, n, q0, q1, k, nmax, list, kept, out_idx, dbg);
+    else if (KSM == 6) knn2_launch_scan<6, 128>(ctx, nw, X, Cf, ldc, d, n, q0, q1, k, nmax, list, kept, out_idx, dbg);
+    else if (KSM == 10) knn2_launch_scan<10, 128>(ctx, nw, X, Cf, ldc, d, n, q0, q1, k, nmax, list, kept, out_idx, dbg);
+    else knn2_launch_scan<16, 128>(ctx, nw, X, Cf, ldc, d, n, q0, q1, k, nmax, list, kept, out_idx, dbg);
+  }
   hssk_rt::check_launch();
   if (dbg) {
     long long h[2] = {0, 0};
@@ -843,13 +1198,18 @@ extern "C" int hssk_knn(hssk_ctx* ctx, const double* X, int d, int n, int k, int
   HSSK_API_END
 }
 
+extern "C" long long hssk_knn_filtered_count(hssk_ctx* ctx) { return ctx ? ctx->knn_filtered : 0; }
+
 extern "C" int hssk_kernel_predict(hssk_ctx* ctx, const hssk_kernel_spec* spec, const double* w, const double* T, int m,
                                    double* pred) {
   HSSK_API_BEGIN
   if (m <= 0) return 0;
   check_spec(*spec);
-  if (spec->d > KNN_DMAX) throw std::invalid_argument("hssk_kernel_predict: point dimension must be <= 64");
-  HSSK_LAUNCH(kernel_predict_kernel, dim3((unsigned)((m + PR_T - 1) / PR_T)), dim3(PR_T), 0, ctx->stream, *spec, w, T, m, pred);
+  const dim3 grid((unsigned)((m + PR_T - 1) / PR_T));
+  if (spec->d <= KNN_DMAX) HSSK_LAUNCH(kernel_predict_kernel, grid, dim3(PR_T), 0, ctx->stream, *spec, w, T, m, pred);
+  else if (spec->type == 0) HSSK_LAUNCH((kernel_predict_wide_kernel<0, 32>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, T, m, pred);
+  else if (spec->type == 1) HSSK_LAUNCH((kernel_predict_wide_kernel<1, 32>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, T, m, pred);
+  else HSSK_LAUNCH((kernel_predict_wide_kernel<2, 8>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, T, m, pred);
   hssk_rt::check_launch();
   HSSK_API_END
 }

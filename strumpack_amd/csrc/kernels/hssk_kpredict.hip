@@ -241,6 +241,109 @@ __global__ __launch_bounds__(256) void kp_main_kernel(KpArgs a) {
   }
 }
 
+// ---- beyond KP_DMAX coordinates (hssk_kernel_predict_f32_wide) ----------------------------------------------------------------
+// The difference form only, with the grid, the sums and their order of kp_main_kernel.  A test tile of R^784 is 200 KB, so
+// the coordinates pass through the LDS KPW_DC at a time: the 64 test points' (shared by the four waves) and, per wave, those of
+// the RS training points it meets in a sweep over the coordinates, read back as broadcasts.  (Through uniform loads, as in
+// kp_diff16, RS row addresses and their values outgrow the scalar registers once the coordinate loop is the outer one.)  What the
+// pairs of a lane have accumulated stays in registers across the passes: the distance (Gauss, Laplace: RS = 32) or the p power
+// sums (ANOVA: RS = 16).  Per pair the coordinates are added in order in FP32, exactly the sum of the difference form above: the
+// bound of DESIGN.md 8b holds as it is written in d, no term is added.  Training rows past the last one read the last one and
+// carry the weight zero (wpad), so every wave of a workgroup meets every barrier.
+constexpr int KPW_DC = 64;            // coordinates per pass
+constexpr int KPW_LD = KP_T + 1;      // row stride of the staged test pass (the transposing stores spread over the banks)
+
+__global__ __launch_bounds__(256) void kp_wpad_kernel(const float* __restrict__ w, long long n, int ldn, float* __restrict__ wpad) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < ldn) wpad[i] = i < n ? w[i] : 0.f;
+}
+
+template <int TYPE, int RS>
+__global__ __launch_bounds__(256) void kp_wide_kernel(KpArgs a) {
+  constexpr int NS = TYPE == 2 ? 8 : 1;   // sums a pair carries
+  HSSK_SHARED double red[KP_W * KP_T];
+  HSSK_SHARED float tl[KPW_DC * KPW_LD];       // [coordinate of the pass][test point]
+  HSSK_SHARED float xs[KP_W * RS * KPW_DC];    // per wave: [training point of the sweep][coordinate of the pass]
+  const int tid = threadIdx.x, lane = tid & 63, wv = hssk_uniform(tid >> 6);
+  const int tt = blockIdx.x, sp = blockIdx.y, d = a.d, c0 = tt * KP_T;
+  float* xw = xs + wv * RS * KPW_DC;
+  const long long last = a.n - 1;
+  const long long ch0 = (long long)sp * a.chunks / a.splits, ch1 = (long long)(sp + 1) * a.chunks / a.splits;
+  double dd = 0.;
+  long long ndf = 0;
+  for (long long ch = ch0; ch < ch1; ch++) {
+    const long long r0 = (ch * KP_W + wv) * KP_T;
+    if (r0 <= last) ndf++;
+    for (int i0 = 0; i0 < KP_T; i0 += RS) {
+      const long long rb = r0 + i0;
+      const bool act = rb <= last;                        // (uniform over the wave; a sweep of padding only stages and waits)
+      const int top = act ? (int)min((long long)(RS - 1), last - rb) : 0;
+      const float* xb = a.X + (size_t)(act ? rb : 0) * d;
+      float acc[RS][NS];
+#pragma unroll
+      for (int i = 0; i < RS; i++)
+#pragma unroll
+        for (int q = 0; q < NS; q++) acc[i][q] = 0.f;
+      for (int d0 = 0; d0 < d; d0 += KPW_DC) {
+        const int dc = min(KPW_DC, d - d0);
+        __syncthreads();
+        for (int e = tid; e < KP_T * dc; e += 256) {
+          const int pt = e / dc, j = e % dc;
+          tl[j * KPW_LD + pt] = a.T[(size_t)min(c0 + pt, a.m - 1) * d + d0 + j];
+        }
+        for (int e = lane; e < RS * dc; e += 64) {
+          const int i = e / dc, j = e % dc;
+          xw[i * KPW_DC + j] = xb[(size_t)min(i, top) * d + d0 + j];
+        }
+        __syncthreads();
+        if (act)
+          for (int j = 0; j < dc; j++) {
+            const float t = tl[j * KPW_LD + lane];
+#pragma unroll
+            for (int i = 0; i < RS; i++) {
+              const float df = xw[i * KPW_DC + j] - t;
+              if (TYPE == 2) {
+                const float tmp = exp2f(-(df * df * a.s2));
+                float pw = tmp;
+#pragma unroll
+                for (int q = 0; q < NS; q++)
+                  if (q < a.p) { acc[i][q] += pw; pw *= tmp; }
+              } else {
+                acc[i][0] += TYPE == 0 ? df * df : fabsf(df);
+              }
+            }
+          }
+      }
+      if (act) {
+        // every 16 terms added in FP32 and then to the FP64 sum, as in kp_diff_tile
+#pragma unroll
+        for (int g = 0; g < RS / 16; g++) {
+          const float* wb = a.wpad + rb + 16 * g;
+          float s16 = 0.f;
+#pragma unroll
+          for (int i = 0; i < 16; i++) {
+            float v = 0.f;
+            if (TYPE == 2) {
+              float S[8], Kpp[9] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+              for (int q = 0; q < 8; q++) S[q] = acc[16 * g + i][q < NS ? q : 0];
+              kp_newton<8>(S, Kpp, a.p, v);
+            } else {
+              v = exp2f(-(acc[16 * g + i][0] * a.s2));
+            }
+            s16 += wb[i] * v;
+          }
+          dd += (double)s16;
+        }
+      }
+    }
+  }
+  red[wv * KP_T + lane] = dd;
+  __syncthreads();
+  if (wv == 0) a.partial[(size_t)sp * a.ldm + c0 + lane] = ((red[lane] + red[KP_T + lane]) + red[2 * KP_T + lane]) + red[3 * KP_T + lane];
+  if (lane == 0 && ndf) hssk_gadd_ll(a.dstats + 1, ndf);
+}
+
 // the splits in index order, rounded once
 __global__ __launch_bounds__(256) void kp_reduce_kernel(const double* __restrict__ partial, int ldm, int splits, int m, float* __restrict__ pred) {
   const int c = blockIdx.x * 256 + threadIdx.x;
@@ -323,6 +426,62 @@ extern "C" int hssk_kernel_predict_f32(hssk_ctx* ctx, const float* X, long long 
   else if (KSM == 9) kp_launch_main<9>(ctx, a, nt, shm);
   else if (KSM == 17) kp_launch_main<17>(ctx, a, nt, shm);
   else kp_launch_main<33>(ctx, a, nt, shm);
+  if (stats) { hssk_watch_stop(ctx, 6); hssk_watch_start(ctx, 4); }
+  HSSK_LAUNCH(kp_reduce_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)a.partial, ldm, splits, m, pred);
+  if (stats) hssk_watch_stop(ctx, 4);
+  hssk_rt::check_launch();
+  if (stats) {
+    long long hs[2] = {0, 0};
+    hssk_rt::d2h(hs, a.dstats, 16, ctx->stream);
+    hssk_rt::sync(ctx->stream);
+    const double ms_main = hssk_watch_read_ms(ctx, 6, nullptr), ms_rest = hssk_watch_read_ms(ctx, 4, nullptr);
+    stats[0] = hs[0]; stats[1] = hs[1]; stats[2] = splits;
+    stats[3] = (long long)std::llround((ms_main + ms_rest) * 1e3);
+    stats[4] = (long long)std::llround(ms_main * 1e3);
+    stats[5] = (long long)std::llround(ms_rest * 1e3);
+  }
+  HSSK_API_END
+}
+
+extern "C" int hssk_kernel_predict_f32_wide(hssk_ctx* ctx, const float* X, long long n, int d, int type, int p, double h, const float* w,
+                                            const float* T, int m, float* pred, long long* stats) {
+  HSSK_API_BEGIN
+  if (!ctx) throw std::invalid_argument("hssk_kernel_predict_f32_wide: no context");
+  if (type < 0 || type > 2) throw std::invalid_argument("hssk_kernel_predict_f32_wide: type must be 0 (Gauss), 1 (Laplace) or 2 (ANOVA)");
+  if (d <= KP_DMAX) throw std::invalid_argument("hssk_kernel_predict_f32_wide: point dimension must be above 64 (hssk_kernel_predict_f32 takes the others)");
+  if (type == 2 && (p < 1 || p > 8)) throw std::invalid_argument("hssk_kernel_predict_f32_wide: ANOVA degree must be in [1, 8]");
+  if (n < 0 || n > (1LL << 31) - 1024) throw std::invalid_argument("hssk_kernel_predict_f32_wide: training point count out of range");
+  if (m < 0 || m > (1 << 30)) throw std::invalid_argument("hssk_kernel_predict_f32_wide: test point count out of range");
+  if (!(h > 0.)) throw std::invalid_argument("hssk_kernel_predict_f32_wide: the kernel width must be positive");
+  if ((n > 0 && (!X || !w)) || (m > 0 && (!T || !pred))) throw std::invalid_argument("hssk_kernel_predict_f32_wide: null pointer");
+  if (stats) for (int i = 0; i < 6; i++) stats[i] = 0;
+  if (m == 0) return 0;
+  if (n == 0) {
+    HSSK_LAUNCH(kp_zero_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, pred, m);
+    hssk_rt::check_launch();
+    return 0;
+  }
+  const int chunks = (int)((n + KP_W * KP_T - 1) / (KP_W * KP_T)), nt = (m + KP_T - 1) / KP_T;
+  const int splits = hssk_kernel_predict_splits(n, m), ldn = chunks * KP_W * KP_T, ldm = nt * KP_T;
+  // scratch: statistics | padded weights | partial sums
+  const size_t o_st = 0, o_wp = 256, o_pa = kp_align(o_wp + sizeof(float) * (size_t)ldn);
+  char* base = (char*)ctx->scratch(o_pa + sizeof(double) * (size_t)splits * ldm);
+  const double l2e = 1.4426950408889634;
+  KpArgs a;
+  a.X = X; a.T = T; a.Xa = nullptr; a.Ta = nullptr; a.wpad = (float*)(base + o_wp); a.xmax = nullptr; a.tmax = nullptr;
+  a.n = n; a.m = m; a.d = d; a.type = type; a.p = type == 2 ? p : 1; a.ldn = ldn; a.ldm = ldm; a.chunks = chunks; a.splits = splits;
+  a.force_diff = 1;
+  a.s2 = (float)(type == 1 ? l2e / h : l2e / (2. * h * h));
+  a.partial = (double*)(base + o_pa);
+  a.dstats = (long long*)(base + o_st);
+  hssk_rt::memset_async(a.dstats, 0, 16, ctx->stream);
+  if (stats) hssk_watch_start(ctx, 4);
+  HSSK_LAUNCH(kp_wpad_kernel, dim3((unsigned)((ldn + 255) / 256)), dim3(256), 0, ctx->stream, w, n, ldn, (float*)(base + o_wp));
+  if (stats) { hssk_watch_stop(ctx, 4); hssk_watch_start(ctx, 6); }
+  const dim3 grid((unsigned)nt, (unsigned)splits);
+  if (type == 0) HSSK_LAUNCH((kp_wide_kernel<0, 32>), grid, dim3(256), 0, ctx->stream, a);
+  else if (type == 1) HSSK_LAUNCH((kp_wide_kernel<1, 32>), grid, dim3(256), 0, ctx->stream, a);
+  else HSSK_LAUNCH((kp_wide_kernel<2, 16>), grid, dim3(256), 0, ctx->stream, a);
   if (stats) { hssk_watch_stop(ctx, 6); hssk_watch_start(ctx, 4); }
   HSSK_LAUNCH(kp_reduce_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)a.partial, ldm, splits, m, pred);
   if (stats) hssk_watch_stop(ctx, 4);

@@ -159,13 +159,13 @@ HSSK_SYMBOLS = [
     "hssk_sumsq_vbatched", "hssk_shift_diag", "hssk_mfma_f64_peak_tflops", "hssk_memcpy_d2d",
     "hssk_memcpy2d_h2d", "hssk_memcpy2d_d2h", "hssk_memset_zero", "hssk_is_device_pointer",
     "hssk_basis_dense", "hssk_mfma_f64_probe", "hssk_last_dgemm_clock_ghz", "hssk_leaf_update_vbatched", "hssk_formq_vbatched",
-    "hssk_kernel_eval_vbatched", "hssk_knn", "hssk_kernel_predict", "hssk_copy_triu",
+    "hssk_kernel_eval_vbatched", "hssk_knn", "hssk_knn_filtered_count", "hssk_kernel_predict", "hssk_copy_triu",
     "hssk_laswp_vbatched", "hssk_shift_diag_cplx", "hssk_upload_async", "hssk_h2d_block_async", "hssk_h2d_bytes_async", "hssk_expand_image", "hssk_copy_fence", "hssk_compute_fence", "hssk_compute_mark", "hssk_copy_wait", "hssk_id_xsolve_vbatched", "hssk_id_solves_inline", "hssk_gather_combine", "hssk_ulv_split", "hssk_tpqr_vbatched", "hssk_fill_toeplitz_block", "hssk_sum_slabs", "hssk_ulv_fwd_sweep", "hssk_ulv_bwd_sweep", "hssk_apply_sweep", "hssk_sweep_status", "hssk_sweep_arm", "hssk_trtri_diag_vbatched", "hssk_sjlt_dense", "hssk_sjlt_sketch",
     "hssk_plan_begin", "hssk_plan_end", "hssk_plan_replay", "hssk_plan_destroy", "hssk_plan_size",
     "hssk_sketch_gen", "hssk_gen_elems", "hssk_gen_fill", "hssk_colsets", "hssk_colsets_max_universe",
     "hssk_cluster_median", "hssk_pchol_id_vbatched", "hssk_pchol_id_max_m", "hssk_pchol_id_rank_cap", "hssk_sum_partials", "hssk_gram_vbatched", "hssk_gram_gen_vbatched", "hssk_gram_gen_supported",
     "hssk_sgemm_sketch", "hssk_narrow_f32", "hssk_gather_elems_f32",
-    "hssk_kernel_predict_f32", "hssk_kernel_predict_splits",
+    "hssk_kernel_predict_f32", "hssk_kernel_predict_f32_wide", "hssk_kernel_predict_splits",
 ]
 
 
@@ -277,10 +277,13 @@ class Hssk:
         L.hssk_shift_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double]
         L.hssk_kernel_eval_vbatched.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.hssk_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.hssk_knn_filtered_count.argtypes = [C.c_void_p]
+        L.hssk_knn_filtered_count.restype = C.c_longlong
         L.hssk_kernel_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         # float points / weights / output; the last argument: 6 host long longs (may be None)
-        L.hssk_kernel_predict_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_double,
-                                              C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        for fn in ("hssk_kernel_predict_f32", "hssk_kernel_predict_f32_wide"):     # (the second: d >= 65)
+            getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_double,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.hssk_kernel_predict_splits.argtypes = [C.c_longlong, C.c_int]
         L.hssk_colsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.hssk_cluster_median.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -326,16 +329,17 @@ class Hssk:
         return d.set(a)
 
     def kernel_predict_f32(self, X, w, T, ktype, h, p=1, stats=False):
-        """sum_r w[r] k(x_r, t_c) for float32 points X (n x d) and T (m x d) through hssk_kernel_predict_f32: returns the m
-        float32 predictions (and the 6 statistics of include/hssk.h when stats is set)"""
+        """sum_r w[r] k(x_r, t_c) for float32 points X (n x d) and T (m x d) through hssk_kernel_predict_f32 (d <= 64) or
+        hssk_kernel_predict_f32_wide (d >= 65): returns the m float32 predictions (and the 6 statistics of include/hssk.h when
+        stats is set)"""
         X = np.ascontiguousarray(X, dtype=np.float32)
         T = np.ascontiguousarray(T, dtype=np.float32)
         w = np.ascontiguousarray(w, dtype=np.float32)
         (n, d), m = X.shape, T.shape[0]
         dX, dT, dw, dp = (self.array(X.ravel()), self.array(T.ravel()), self.array(w), self.empty((m,), np.float32))
         st = np.zeros(6, dtype=np.int64)
-        self.check(self.lib.hssk_kernel_predict_f32(self.ctx, dX.ptr, n, d, ktype, p, h, dw.ptr, dT.ptr, m, dp.ptr,
-                                                    st.ctypes.data if stats else None))
+        fn = self.lib.hssk_kernel_predict_f32 if d <= 64 else self.lib.hssk_kernel_predict_f32_wide
+        self.check(fn(self.ctx, dX.ptr, n, d, ktype, p, h, dw.ptr, dT.ptr, m, dp.ptr, st.ctypes.data if stats else None))
         out = dp.get()
         for a in (dX, dT, dw, dp):
             a.free()
