@@ -283,6 +283,15 @@ int hssk_cluster_median(hssk_ctx* ctx, double* X, int d, int n, int algo, int cl
 /* pred[c] = sum_r w[r] k(x_r, t_c), c < m; T is d x m (device)   (Kernel::predict, kernel/KernelRegression.hpp:112-123).
  * Any d >= 1: beyond 64 coordinates the points pass through the LDS 32 coordinates at a time, same arithmetic per pair. */
 int hssk_kernel_predict(hssk_ctx* ctx, const hssk_kernel_spec* spec, const double* w, const double* T, int m, double* pred);
+/* out(r, c) = k(x_r, t_c), r < n, c < m: the cross-kernel block of the training points against m test points (T: d x m, device),
+ * n x m column-major with leading dimension ldo >= n; no lambda term; the rows n .. ldo - 1 are not touched.  Any d >= 1.  The
+ * arithmetic of a pair is that of hssk_kernel_predict. */
+int hssk_kernel_cross(hssk_ctx* ctx, const hssk_kernel_spec* spec, const double* T, int m, double* out, long long ldo);
+/* pred[c] = sum_r W(r, c) k(x_r, t_c): the prediction sum with a weight column per test point (W: n x m, ldw >= n, device).  The
+ * kernel values are evaluated again, not read; per test point the pairs are added in training order, as in hssk_kernel_predict.
+ * With W = (K + lambda I)^-1 k(X, T) this is the quadratic form of the predictive variance. */
+int hssk_kernel_predict_cols(hssk_ctx* ctx, const hssk_kernel_spec* spec, const double* W, long long ldw, const double* T, int m,
+                             double* pred);
 /* The promise of the single-precision prediction's matrix-core route: the worst relative error the norm expansion
  * |x|^2 + |t|^2 - 2 x.t can add to a term w_r k(x_r, t_c).  A (training tile, test tile) pair whose scaled norms would exceed it,
  * 4 (d + 4) 2^-24 (max |x~|^2 + max |t~|^2) > tau, is computed from FP32 differences instead. */
@@ -831,6 +840,15 @@ int hssk_shift_diag(hssk_ctx* ctx, const hssk_shift_desc* descs, int count, doub
 /* the same for the real 2n x 2n image [re -im; im re] (entries interleaved) of a complex matrix: adds the image of
  * (re + i im) I, i.e. A(k,k) += re, A(2j, 2j+1) -= im, A(2j+1, 2j) += im; n (the real dimension) must be even */
 int hssk_shift_diag_cplx(hssk_ctx* ctx, const hssk_shift_desc* descs, int count, double re, double im);
+/* partial[k] = sum_{i < n} log|A_k(i, i)| for every descriptor, out[0] = the sum of the partials in index order (partial:
+ * device, count doubles; out: device, 1 double; count = 0 gives 0.0).  The log|det| of triangular factors: DeviceHSS::logabsdet
+ * lists the triangles of the ULV factorization.  Fixed summation order, no atomics: bitwise repeatable.  IEEE values throughout
+ * (a zero on a diagonal gives -inf). */
+typedef struct hssk_logdet_desc {
+  const double* A;
+  int n, lda;
+} hssk_logdet_desc;
+int hssk_logabsdet_vbatched(hssk_ctx* ctx, const hssk_logdet_desc* descs, int count, double* partial, double* out);
 /* peak-rate probe: runs a dependent-free v_mfma_f64_16x16x4_f64 loop on every CU and returns the
  * measured TFLOP/s (used by bench.py to confirm the FP64 matrix roof on the box) */
 double hssk_mfma_f64_peak_tflops(hssk_ctx* ctx, int iters);

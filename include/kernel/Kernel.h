@@ -54,6 +54,30 @@ int SPX_kernel_set_neighbors(STRUMPACKKernel K, int k, const int* ann);
  * in permuted order) */
 int SPX_kernel_permutation(STRUMPACKKernel K, int* perm);
 int SPX_kernel_weights(STRUMPACKKernel K, double* w);
+/* ---- the kept model: log-determinant, log marginal likelihood, predictive variance, a new lambda without a new compression.
+ * Double handles with a built-in kernel.  SPX_kernel_keep_model(K, 1) before the fit makes STRUMPACK_kernel_fit_HSS_double keep the
+ * factored HSS matrix, the cluster-ordered points in HBM, the permuted labels and the weights until the next fit,
+ * SPX_kernel_keep_model(K, 0) or the destroy call; without it the fit keeps nothing, as before.  Every call below returns
+ * non-zero, its outputs untouched, without a kept model, on a float handle and for a user-defined kernel. */
+int SPX_kernel_keep_model(STRUMPACKKernel K, int keep);
+/* *out = log|det H|, H the compressed K + lambda I (read off the ULV factors) */
+int SPX_kernel_logabsdet(STRUMPACKKernel K, double* out);
+/* *out = -1/2 y^T alpha - 1/2 log|det H| - n/2 log(2 pi)   (y: the permuted labels, alpha: the weights) */
+int SPX_kernel_log_marginal_likelihood(STRUMPACKKernel K, double* out);
+/* var[c] = k(t_c, t_c) - k_c^T H^-1 k_c for the m test points (test: d x m): the variance of the latent function -- add lambda for
+ * the observation noise.  Not clamped: H equals K + lambda I only up to the compression tolerance, so a value may be slightly
+ * negative.  Works in chunks of 64 test points (cross-kernel block, device solve in place, column-weighted sum). */
+int SPX_kernel_predict_variance_double(STRUMPACKKernel K, int m, const double* test, double* var);
+/* device-clock milliseconds of the last variance call: out[0] cross-kernel blocks, [1] solves, [2] column sums */
+int SPX_kernel_variance_ms(STRUMPACKKernel K, double* out);
+/* a new lambda: shift(lambda - current), factor, solve of the kept labels.  The handle's weights and lambda are the new ones
+ * afterwards (STRUMPACK_kernel_predict_double, SPX_kernel_weights and the calls above see them); ranks and tree are unchanged. */
+int SPX_kernel_model_set_lambda(STRUMPACKKernel K, double lambda);
+/* the kept matrix through HSSMatrix::write (layout: csrc/host/hss_io.cpp) */
+int SPX_kernel_model_write(STRUMPACKKernel K, const char* path);
+/* the kept labels (n doubles) and the training points (d x n), both in cluster order */
+int SPX_kernel_model_labels(STRUMPACKKernel K, double* y);
+int SPX_kernel_model_points(STRUMPACKKernel K, double* x);
 /* binary_tree_clustering on its own (clustering/Clustering.hpp:143-168): algo 0 natural, 1 2means, 2 kdtree,
  * 3 pca, 4 cobble; data (d x n) is reordered in place, perm is 1-based; returns the number of leaves and writes
  * at most cap leaf sizes */

@@ -250,6 +250,10 @@ int SPX_d_struct_extract_blocks(const CSPStructMat S, int nb, const int* rows, c
  * pre-order its dimensions, ranks and blocks D, B01, B10, XU, permU, Ir, XV, permV, Ic (layout: csrc/host/hss_io.cpp).  HSS only,
  * single process. */
 int SPX_d_struct_write(const CSPStructMat S, const char* path);
+/* *out = log|det H| of a factored HSS matrix, read off the triangles of its ULV factors (one launch; no sign).  Non-zero, with
+ * *out untouched: before SP_d_struct_factor, after a shift or a partial factorization, on more than one process, for a BLR
+ * matrix. */
+int SPX_d_struct_logabsdet(const CSPStructMat S, double* out);
 /* ---- BLR frontal matrix: partial factorization of F = [F11 F12; F21 F22] -- what the reference's sparse BLR fronts call,
  * BLR::BLRMatrix<T>::construct_and_partial_factor(A11, A12, A21, A22, B11, B12, B21, tiles1, tiles2, admissible, opts)
  * (BLR/BLRMatrix.hpp:186-194, BLR/BLRMatrix.cpp:740-1037, algorithm RL = its default; batched GPU precedent

@@ -34,7 +34,7 @@ SP_SYMBOLS = [
     "SPX_d_struct_from_dense_device_comm", "SPX_d_struct_from_blocks_device", "SPX_d_struct_from_blocks_device_cb",
     "SPX_d_struct_from_kernel_comm",
     "SPX_d_struct_from_generator", "SPX_d_struct_from_generator_comm", "SPX_d_struct_from_generator_sharded",
-    "SPX_d_struct_extract_blocks", "SPX_d_struct_write",
+    "SPX_d_struct_extract_blocks", "SPX_d_struct_write", "SPX_d_struct_logabsdet",
     "SPX_d_blr_front_factor", "SPX_d_blr_front_factor_device", "SPX_d_blr_front_time_phases", "SPX_blr_low_rank_algorithm", "SPX_d_blr_front_forward",
     "SPX_d_blr_front_backward", "SPX_d_blr_front_schur", "SPX_d_blr_front_schur_device", "SPX_d_blr_front_tile_ranks",
     "SPX_d_blr_front_stats", "SPX_d_blr_front_destroy",
@@ -104,6 +104,7 @@ def load(path):
     L.SPX_d_struct_mult_device.argtypes = [vp, C.c_char, C.c_int, dp, C.c_longlong, dp, C.c_longlong]
     L.SPX_d_struct_solve_device.argtypes = [vp, C.c_int, dp, C.c_longlong]
     L.SPX_d_struct_node_info.argtypes = [vp, C.POINTER(C.c_int)]
+    L.SPX_d_struct_logabsdet.argtypes = [vp, C.POINTER(C.c_double)]
     L.SPX_d_struct_stats.argtypes = [vp, C.POINTER(C.c_double)]
     ll = C.c_longlong
     L.SPX_d_struct_partial_factor.argtypes = [vp]
@@ -478,6 +479,13 @@ class StructuredMatrix:
     def shift(self, s):
         if self.L.SP_d_struct_shift(self.h, s):
             raise RuntimeError("SP_d_struct_shift failed")
+
+    def logabsdet(self):
+        """log|det H| from the ULV factors (after factor(); a shift invalidates them)"""
+        out = C.c_double(0.0)
+        if self.L.SPX_d_struct_logabsdet(self.h, C.byref(out)):
+            raise RuntimeError("SPX_d_struct_logabsdet failed")
+        return out.value
 
     def mult_device(self, dB, dC, nrhs, trans="N"):
         if self.L.SPX_d_struct_mult_device(self.h, trans.encode(), nrhs, dB, self.n, dC, self.n):

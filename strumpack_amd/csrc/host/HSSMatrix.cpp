@@ -388,6 +388,11 @@ void HSSMatrix<double>::backward_solve(WorkSolve<double>& w, DenseM_t& x) const 
   w.x = DenseM_t();
 }
 void HSSMatrix<double>::shift(scalar_t sigma) { owner("shift"); eng_->shift(sigma); }
+double HSSMatrix<double>::logabsdet() const {
+  if (veng_) throw std::logic_error("logabsdet: not available on a child view (the factors of a child are those of its own subtree)");
+  if (!eng_) throw std::logic_error("logabsdet: the HSS matrix is not compressed");
+  return eng_->logabsdet();
+}
 void HSSMatrix<double>::mult_device(Trans op, int nrhs, const double* dx, long long ldx, double* dy, long long ldy, double beta) const {
   if (veng_) veng_->mult_node(vnode_, op == Trans::N ? 'N' : 'C', nrhs, dx, ldx, dy, ldy, true, beta);
   else eng_->mult(op == Trans::N ? 'N' : 'C', nrhs, dx, ldx, dy, ldy, true, beta);

@@ -111,6 +111,8 @@ template <> class HSSMatrix<double> : public structured::StructuredMatrix<double
   void solve(DenseM_t& b) const override;
   using structured::StructuredMatrix<double>::solve;
   void shift(scalar_t sigma) override;
+  // extension: log|det H| from the ULV factors (after factor(); not on a child view, not after partial_factor() or shift())
+  double logabsdet() const;
   DenseM_t dense() const;
   // H(I, J) and H(i, j) (reference: HSSMatrix.extract.hpp:36-104): tree traversal on the device
   DenseM_t extract(const std::vector<std::size_t>& I, const std::vector<std::size_t>& J) const;

@@ -24,8 +24,105 @@ thread_local std::vector<int> last_nodes;
 void ckk(int rc) { if (rc) throw std::runtime_error(hssk_last_error()); }
 }  // namespace
 
+// ---- the kept model of Kernel<double> ------------------------------------------------------------------------------------------
+struct Kernel<double>::Model {
+  HSS::HSSMatrix<double> H;            // compressed K + lambda I with its ULV factors
+  std::vector<double> labels;          // in cluster order
+  DenseMatrix<double> weights;
+  double* dX = nullptr;                // cluster-ordered points, d x n (device pool)
+  size_t bX = 0;
+  explicit Model(HSS::HSSMatrix<double>&& h) : H(std::move(h)) {}
+  hssk_ctx* ctx() const { return H.engine()->ctx(); }
+  ~Model() {
+    if (dX) {
+      hssk_sync(ctx());   // (nothing in flight may still read the chunk)
+      DevicePool::get().release(dX, bX);
+    }
+  }
+};
+
+Kernel<double>::Kernel(DenseM_t& data, scalar_t lambda) : data_(data), lambda_(lambda) {}
+Kernel<double>::~Kernel() = default;
+void Kernel<double>::keep_model(bool keep) {
+  keep_model_ = keep;
+  if (!keep) model_.reset();
+}
+bool Kernel<double>::has_model() const { return bool(model_); }
+const Kernel<double>::Model& Kernel<double>::model(const char* what) const {
+  if (!model_) throw std::logic_error(std::string(what) + ": no kept model (keep_model(true) before fit_HSS; built-in kernels only)");
+  return *model_;
+}
+double Kernel<double>::logabsdet() const { return model("logabsdet").H.logabsdet(); }
+const std::vector<double>& Kernel<double>::model_labels() const { return model("model_labels").labels; }
+const DenseMatrix<double>& Kernel<double>::model_weights() const { return model("model_weights").weights; }
+void Kernel<double>::model_write(const std::string& path) const { model("model_write").H.write(path); }
+
+double Kernel<double>::log_marginal_likelihood() const {
+  const Model& M = model("log_marginal_likelihood");
+  const double ld = M.H.logabsdet();
+  long double ya = 0.L;
+  for (std::size_t i = 0; i < M.labels.size(); i++) ya += (long double)M.labels[i] * (long double)M.weights(i, 0);
+  const long double two_pi = 6.283185307179586476925286766559L;
+  return (double)(-0.5L * ya - 0.5L * (long double)ld - 0.5L * (long double)M.labels.size() * std::log(two_pi));
+}
+
+DenseMatrix<double> Kernel<double>::model_set_lambda(double lambda) {
+  model("model_set_lambda");
+  Model& M = *model_;
+  M.H.shift(lambda - lambda_);
+  lambda_ = lambda;
+  M.H.factor();
+  DenseMatrix<double> w(n(), 1, M.labels.data(), n());
+  M.H.solve(w);
+  M.weights = w;
+  return w;
+}
+
+std::vector<double> Kernel<double>::predict_variance(const DenseMatrix<double>& test) const {
+  const Model& M = model("predict_variance");
+  if (test.rows() != d()) throw std::invalid_argument("predict_variance: test points have the wrong dimension");
+  const int m = int(test.cols()), dim = int(d()), CH = 64;
+  const long long nn = (long long)n();
+  std::vector<double> var(m, 0.);
+  var_ms_[0] = var_ms_[1] = var_ms_[2] = 0.;
+  if (m == 0) return var;
+  hssk_ctx* ctx = M.ctx();
+  struct Buf {   // a device pool chunk for the length of the call
+    void* p = nullptr; size_t bytes; hssk_ctx* ctx;
+    Buf(hssk_ctx* c, size_t b) : bytes(std::max<size_t>(b, 256)), ctx(c) { p = DevicePool::get().acquire(bytes); if (!p) throw std::runtime_error(hssk_last_error()); }
+    ~Buf() { hssk_sync(ctx); DevicePool::get().release(p, bytes); }
+  };
+  Buf bT(ctx, sizeof(double) * dim * m), bK(ctx, sizeof(double) * nn * CH), bD(ctx, sizeof(double) * CH * CH), bP(ctx, sizeof(double) * m);
+  double *dT = (double*)bT.p, *dK = (double*)bK.p, *dD = (double*)bD.p, *dP = (double*)bP.p;
+  ckk(hssk_memcpy2d_h2d(ctx, dT, sizeof(double) * dim, test.data(), sizeof(double) * test.ld(), sizeof(double) * dim, m));
+  std::vector<double> ktt(m, 0.), quad(m, 0.);
+  const hssk_kernel_spec spec{M.dX, nn, dim, device_type(), degree(), width(), 0.};
+  for (int c0 = 0; c0 < m; c0 += CH) {
+    const int mc = std::min(CH, m - c0);
+    const double* dTc = dT + (size_t)c0 * dim;
+    hssk_watch_start(ctx, 1);
+    ckk(hssk_kernel_cross(ctx, &spec, dTc, mc, dK, nn));
+    hssk_watch_stop(ctx, 1);
+    // k(t_c, t_c) by the same pair function: the diagonal of the chunk's own kernel block
+    const hssk_kernel_spec self{dTc, (long long)mc, dim, device_type(), degree(), width(), 0.};
+    ckk(hssk_kernel_cross(ctx, &self, dTc, mc, dD, mc));
+    ckk(hssk_memcpy2d_d2h(ctx, ktt.data() + c0, sizeof(double), dD, sizeof(double) * (mc + 1), sizeof(double), mc));
+    hssk_watch_start(ctx, 2);
+    M.H.solve_device(mc, dK, nn);
+    hssk_watch_stop(ctx, 2);
+    hssk_watch_start(ctx, 3);
+    ckk(hssk_kernel_predict_cols(ctx, &spec, dK, nn, dTc, mc, dP + c0));
+    hssk_watch_stop(ctx, 3);
+  }
+  ckk(hssk_memcpy_d2h(ctx, quad.data(), dP, (long long)sizeof(double) * m));
+  for (int w = 0; w < 3; w++) var_ms_[w] = hssk_watch_read_ms(ctx, w + 1, nullptr);
+  for (int c = 0; c < m; c++) var[c] = ktt[c] - quad[c];
+  return var;
+}
+
 DenseMatrix<double> Kernel<double>::fit_HSS(std::vector<double>& labels, const HSS::HSSOptions<double>& opts) {
   if (labels.size() != n()) throw std::invalid_argument("fit_HSS: one label per training point expected");
+  model_.reset();   // (the model of an earlier fit goes before the new compression asks for memory)
   double t0 = now();
   if (opts.verbose()) std::cout << "# starting HSS compression..." << std::endl;
   HSS::HSSMatrix<double> H(*this, opts);
@@ -56,6 +153,16 @@ DenseMatrix<double> Kernel<double>::fit_HSS(std::vector<double>& labels, const H
   last_nodes.assign(6 * (size_t)H.engine()->num_nodes(), 0);
   H.engine()->node_info(last_nodes.data());
   last_fit.v[5] = (long long)((t1 - t0) * 1e6); last_fit.v[6] = (long long)((t2 - t1) * 1e6); last_fit.v[7] = (long long)((t3 - t2) * 1e6);
+  if (keep_model_ && device_type() >= 0 && n() > 0) {
+    std::unique_ptr<Model> M(new Model(std::move(H)));
+    M->labels = labels;
+    M->weights = weights;
+    M->bX = sizeof(double) * d() * n();
+    M->dX = (double*)DevicePool::get().acquire(M->bX);
+    if (!M->dX) throw std::runtime_error(hssk_last_error());
+    ckk(hssk_memcpy2d_h2d(M->ctx(), M->dX, sizeof(double) * d(), data_.data(), sizeof(double) * data_.ld(), sizeof(double) * d(), (long long)n()));
+    model_ = std::move(M);
+  }
   return weights;
 }
 
@@ -468,6 +575,89 @@ int SPX_kernel_weights(STRUMPACKKernel K, double* w) {
   std::copy(kr->weights.data(), kr->weights.data() + kr->weights.rows(), w);
   return 0;
 }
+// ---- the kept model (double handles, built-in kernels): every call returns non-zero, outputs untouched, without one
+namespace {
+kernel::Kernel<double>* model_of(STRUMPACKKernel K) {
+  auto kr = static_cast<KernelRegression*>(K);
+  if (!kr || kr->precision != 0 || !kr->K || kr->K->device_type() < 0 || !kr->K->has_model()) return nullptr;
+  return kr->K.get();
+}
+}  // namespace
+int SPX_kernel_keep_model(STRUMPACKKernel K, int keep) {
+  try {
+    auto kr = static_cast<KernelRegression*>(K);
+    if (!kr || kr->precision != 0 || !kr->K || kr->K->device_type() < 0) return 1;
+    kr->K->keep_model(keep != 0);
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_logabsdet(STRUMPACKKernel K, double* out) {
+  try {
+    auto k = model_of(K);
+    if (!k || !out) return 1;
+    const double v = k->logabsdet();
+    *out = v;
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_log_marginal_likelihood(STRUMPACKKernel K, double* out) {
+  try {
+    auto k = model_of(K);
+    if (!k || !out) return 1;
+    const double v = k->log_marginal_likelihood();
+    *out = v;
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_predict_variance_double(STRUMPACKKernel K, int m, const double* test, double* var) {
+  try {
+    auto k = model_of(K);
+    if (!k || m < 0 || (m > 0 && (!test || !var))) return 1;
+    DenseMatrix<double> t(k->d(), m, test, k->d());
+    const std::vector<double> v = k->predict_variance(t);
+    std::copy(v.begin(), v.end(), var);
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_variance_ms(STRUMPACKKernel K, double* out) {
+  auto k = model_of(K);
+  if (!k || !out) return 1;
+  std::copy(k->variance_ms(), k->variance_ms() + 3, out);
+  return 0;
+}
+int SPX_kernel_model_set_lambda(STRUMPACKKernel K, double lambda) {
+  try {
+    auto k = model_of(K);
+    if (!k) return 1;
+    static_cast<KernelRegression*>(K)->weights = k->model_set_lambda(lambda);
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_model_write(STRUMPACKKernel K, const char* path) {
+  try {
+    auto k = model_of(K);
+    if (!k || !path) return 1;
+    k->model_write(path);
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_model_labels(STRUMPACKKernel K, double* y) {
+  try {
+    auto k = model_of(K);
+    if (!k || !y) return 1;
+    std::copy(k->model_labels().begin(), k->model_labels().end(), y);
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_model_points(STRUMPACKKernel K, double* x) {
+  try {
+    auto k = model_of(K);
+    if (!k || !x) return 1;
+    for (std::size_t i = 0; i < k->n(); i++) std::copy(k->data().ptr(0, i), k->data().ptr(0, i) + k->d(), x + i * k->d());
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+
 int SPX_clustering(int n, int d, double* data, int algo, int leaf_size, int* perm, int* leaf_sizes, int cap) {
   try {
     DenseMatrix<double> p(d, n, data, d);

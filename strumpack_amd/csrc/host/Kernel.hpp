@@ -48,8 +48,10 @@ template <> class Kernel<double> {
   using DenseM_t = DenseMatrix<double>;
 
  public:
-  Kernel(DenseM_t& data, scalar_t lambda) : data_(data), lambda_(lambda) {}
-  virtual ~Kernel() = default;
+  Kernel(DenseM_t& data, scalar_t lambda);
+  virtual ~Kernel();
+  Kernel(const Kernel&) = delete;
+  Kernel& operator=(const Kernel&) = delete;
 
   std::size_t n() const { return data_.cols(); }
   std::size_t d() const { return data_.rows(); }
@@ -68,6 +70,30 @@ template <> class Kernel<double> {
   DenseM_t fit_HSS(std::vector<scalar_t>& labels, const HSS::HSSOptions<scalar_t>& opts);
   // prediction[c] = sum_r weights(r) k(x_r, test_c)
   std::vector<scalar_t> predict(const DenseM_t& test, const DenseM_t& weights) const;
+
+  // ---- extension: the fitted model kept for what a Gaussian-process reading of the fit needs (Kernel.cpp).
+  // keep_model(true) before fit_HSS: the fit then keeps the factored HSS matrix, the cluster-ordered points in HBM, the permuted
+  // labels and the weights until the next fit, keep_model(false) or the destructor.  Off by default: the fit and its memory
+  // are then what they were.  Built-in kernels only (device_type() >= 0); every call below throws without a kept model.
+  void keep_model(bool keep);
+  bool has_model() const;
+  // log|det(H)|, H the compressed K + lambda I, from the ULV factors (HSSMatrix::logabsdet)
+  scalar_t logabsdet() const;
+  // -1/2 y^T alpha - 1/2 log|det H| - n/2 log(2 pi), y the permuted labels, alpha the weights (the dot product in long double)
+  scalar_t log_marginal_likelihood() const;
+  // var[c] = k(t_c, t_c) - k_c^T H^-1 k_c, k_c = k(X, t_c): the variance of the latent function at the test points (add lambda
+  // for the observation noise).  Not clamped: H is K + lambda I only up to the compression tolerance, so a value may come out
+  // slightly negative.  Chunks of 64 test points: cross-kernel block, device solve in place, column-weighted sum.
+  std::vector<scalar_t> predict_variance(const DenseM_t& test) const;
+  // a new lambda without a new compression: shift(lambda - current), factor, solve of the kept labels; returns the new weights,
+  // which the model keeps, and lambda() is the new one afterwards
+  DenseM_t model_set_lambda(scalar_t lambda);
+  // the kept matrix through HSSMatrix::write (with the current lambda on the diagonal of its leaves)
+  void model_write(const std::string& path) const;
+  const std::vector<scalar_t>& model_labels() const;
+  const DenseM_t& model_weights() const;
+  // device-clock milliseconds of the last predict_variance: cross-kernel blocks, solves, column sums (profiling)
+  const double* variance_ms() const { return var_ms_; }
 
   const DenseM_t& data() const { return data_; }
   DenseM_t& data() { return data_; }
@@ -93,6 +119,13 @@ template <> class Kernel<double> {
   std::vector<int> perm_, user_ann_;
   int user_k_ = 0;
   virtual scalar_t eval_kernel_function(const scalar_t* x, const scalar_t* y) const = 0;
+
+ private:
+  struct Model;   // HSS matrix, device points, labels, weights (Kernel.cpp)
+  std::unique_ptr<Model> model_;
+  bool keep_model_ = false;
+  mutable double var_ms_[3] = {0., 0., 0.};
+  const Model& model(const char* what) const;
 };
 
 template <typename scalar_t> class GaussKernel;

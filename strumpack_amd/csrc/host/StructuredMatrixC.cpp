@@ -574,6 +574,14 @@ int SPX_d_struct_write(const CSPStructMat S, const char* path) {
   hss(S)->write(path);
   SP_CATCH
 }
+int SPX_d_struct_logabsdet(const CSPStructMat S, double* out) {
+  SP_TRY
+  if (!hss(S)) throw std::invalid_argument("logabsdet: not an HSS matrix");
+  if (!out) throw std::invalid_argument("logabsdet: no output");
+  const double v = hss(S)->logabsdet();
+  *out = v;
+  SP_CATCH
+}
 
 // ---- BLR frontal matrix (BLRMatrix::construct_and_partial_factor, BLR/BLRMatrix.cpp:740-1037) -------------------------
 extern "C++" {

@@ -187,6 +187,9 @@ class DeviceHSS {
   void factor();
   void solve(int nrhs, double* b, long long ldb, bool on_device);
   void shift(double sigma);
+  // log|det H| read off the triangles of the ULV factors (extension; hss_factor.cpp).  Needs factor() on a single-process
+  // matrix; throws after shift(), partial_factor() or factor_node()
+  double logabsdet();
   // back to the uncompressed state (tree kept): HSSMatrix::reset
   void reset() { OpGuard g(op_mu_); reset_compression(); }
   // the matrix is the real image [re -im; im re] (interleaved) of a complex one: adds the image of (re + i im) I

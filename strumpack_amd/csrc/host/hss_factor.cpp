@@ -346,5 +346,37 @@ void DeviceHSS::factor_sub(int sr, bool partial) {
   stats_.t_factor = now() - t0;
 }
 
+// log|det H| from the ULV factors.  At a non-root node the row transform [I 0; -E I] P^T has determinant +-1 and
+// the Q of the LQ factorization is orthogonal; the m - r unknowns it eliminates carry the triangular factor L, kept transposed in
+// Rlq (m x (m - r), ld m, upper triangular in its first m - r rows -- by the fused node kernel, the split kernel and the
+// gather + blocked-QR path alike); the reduced block moves into the parent.  A node with m == r eliminates nothing.  The root
+// adds the diagonal of its LU.  One launch over all of them; the sign is not available (the reflector counts are not kept).
+double DeviceHSS::logabsdet() {
+  OpGuard op_guard(op_mu_);
+  ensure_ready("logabsdet");
+  if (o_.world != 1) throw std::logic_error("logabsdet: needs a single-process matrix");
+  if (partial_factored_) throw std::logic_error("logabsdet: the factors come from partial_factor() (the (1,1) block is not eliminated)");
+  if (!factored_) throw std::logic_error("logabsdet: factor() has not been called (or shift() invalidated the factors)");
+  std::vector<hssk_logdet_desc> d;
+  for (size_t id = 0; id < nodes_.size(); id++) {
+    const Node& nd = nodes_[id];
+    if (id == 0) {
+      const int mu = nd.leaf() ? nd.m : nodes_[nd.c0].rU + nodes_[nd.c1].rU;
+      if (mu) d.push_back(hssk_logdet_desc{nd.LU, mu, mu});
+    } else if (nd.mU > nd.rU) {
+      d.push_back(hssk_logdet_desc{nd.Rlq, nd.mU - nd.rU, nd.mU});
+    }
+  }
+  for (auto& e : d)
+    if (!e.A) throw std::logic_error("logabsdet: a factor is missing");
+  const Arena::Mark mk = tmp_->mark();
+  double* part = tmp_->dbl(d.size() + 1);
+  double v = 0.;
+  ck(hssk_logabsdet_vbatched(ctx_, d.data(), (int)d.size(), part + 1, part));
+  ck(hssk_memcpy_d2h(ctx_, &v, part, (long long)sizeof(double)));
+  tmp_->rewind(mk);
+  return v;
+}
+
 }  // namespace HSS
 }  // namespace strumpack

@@ -15,6 +15,7 @@
 // part on the FP32 matrix cores.
 #include "hssk_device.h"
 #include "hssk_internal.h"
+#include "hssk_kpair.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -401,153 +402,6 @@ __global__ __launch_bounds__(KW_Q) void knn_wide_kernel(const double* __restrict
       out_idx[(size_t)q * ldo + s] = K == KNN_EMPTY ? -1 : (int)(K & 0xffffffffu);
     }
   if (ub) ub[q] = worst;
-}
-
-// prediction[c] = sum_r w[r] k(x_r, t_c)   (no lambda: train and test points are different sets)
-constexpr int PR_T = 64;
-__global__ __launch_bounds__(PR_T) void kernel_predict_kernel(hssk_kernel_spec ks, const double* __restrict__ w,
-                                                              const double* __restrict__ T, int m,
-                                                              double* __restrict__ pred) {
-  HSSK_SHARED double xt[PR_T * (KNN_DMAX + 1)];
-  HSSK_SHARED double xr[PR_T * (KNN_DMAX + 1)];
-  HSSK_SHARED double wr[PR_T];
-  const int tid = threadIdx.x, c = blockIdx.x * PR_T + tid, d = ks.d;
-  const bool live = c < m;
-  for (int j = 0; j < d; j++) xt[tid * (KNN_DMAX + 1) + j] = live ? T[(size_t)c * d + j] : 0.;
-  double sum = 0.;
-  for (long long r0 = 0; r0 < ks.n; r0 += PR_T) {
-    __syncthreads();
-    for (int e = tid; e < PR_T * d; e += PR_T) {
-      const int pt = e / d, j = e % d;
-      xr[pt * (KNN_DMAX + 1) + j] = r0 + pt < ks.n ? ks.X[(size_t)(r0 + pt) * d + j] : 0.;
-    }
-    wr[tid] = r0 + tid < ks.n ? w[r0 + tid] : 0.;
-    __syncthreads();
-    const int rend = (int)min((long long)PR_T, ks.n - r0);
-    for (int r = 0; r < rend; r++) {
-      double v;
-      if (ks.type == 2) {
-        double Kss[8], Kpp[9];
-        for (int j = 0; j < ks.p; j++) Kss[j] = 0.;
-        for (int i = 0; i < d; i++) {
-          const double df = xr[r * (KNN_DMAX + 1) + i] - xt[tid * (KNN_DMAX + 1) + i];
-          const double tmp = exp(-(df * df) / (2. * ks.h * ks.h));
-          double pw = tmp;
-          for (int j = 0; j < ks.p; j++) { Kss[j] += pw; pw *= tmp; }
-        }
-        Kpp[0] = 1.;
-        for (int i = 1; i <= ks.p; i++) {
-          double s = 0.;
-          for (int q = 1; q <= i; q++) s += ((q & 1) ? 1. : -1.) * Kpp[i - q] * Kss[q - 1];
-          Kpp[i] = s / i;
-        }
-        v = Kpp[ks.p];
-      } else {
-        double acc = 0.;
-        for (int i = 0; i < d; i++) {
-          const double df = xr[r * (KNN_DMAX + 1) + i] - xt[tid * (KNN_DMAX + 1) + i];
-          acc += ks.type == 0 ? df * df : fabs(df);
-        }
-        v = exp(acc * (ks.type == 0 ? -1. / (2. * ks.h * ks.h) : -1. / ks.h));
-      }
-      sum += wr[r] * v;
-    }
-  }
-  if (live) pred[c] = sum;
-}
-
-// e_E = (1 / E) sum_q (-1)^(q + 1) e_(E - q) s_q for E = 1 .. p, the sums in kernel_predict_kernel's order (every index a
-// constant: the arrays stay in registers)
-template <int E>
-__device__ inline void anova_newton(const double (&S)[8], double (&K)[9], int p, double& v) {
-  anova_newton<E - 1>(S, K, p, v);
-  if (E <= p) {
-    double s = 0.;
-#pragma unroll
-    for (int q = 1; q <= E; q++) s += ((q & 1) ? 1. : -1.) * K[E - q] * S[q - 1];
-    K[E] = s / E;
-    v = K[E];
-  }
-}
-template <>
-__device__ inline void anova_newton<0>(const double (&)[8], double (&K)[9], int, double&) { K[0] = 1.; }
-
-// The same sum beyond KNN_DMAX coordinates: whole points no longer fit the LDS, so a tile of RT training points meets the
-// workgroup's 64 test points in passes of KE_DC coordinates.  What a pair has accumulated -- the distance (Gauss, Laplace) or the
-// p power sums of its per-coordinate exponentials (ANOVA) -- carries across the passes in registers; RT is what the registers
-// hold (32 distances, 8 x 8 power sums).  Per pair the coordinates are met in order and the pairs of a test point in training
-// order, as in kernel_predict_kernel: the same arithmetic, the same error bound.  The test points' pass is staged again for
-// every training tile (one staged value per RT differences).
-template <int TYPE, int RT>
-__global__ __launch_bounds__(PR_T) void kernel_predict_wide_kernel(hssk_kernel_spec ks, const double* __restrict__ w,
-                                                                   const double* __restrict__ T, int m, double* __restrict__ pred) {
-  constexpr int NS = TYPE == 2 ? 8 : 1;   // sums a pair carries
-  HSSK_SHARED double xt[PR_T * (KE_DC + 1)];   // [test point][coordinate of the pass]
-  HSSK_SHARED double xr[RT * KE_DC];           // [training point][coordinate of the pass]: read as broadcasts
-  HSSK_SHARED double wr[RT];
-  const int tid = threadIdx.x, cb = blockIdx.x * PR_T, c = cb + tid, d = ks.d, P = ks.p;
-  const double h2 = 2. * ks.h * ks.h;
-  double sum = 0.;
-  for (long long r0 = 0; r0 < ks.n; r0 += RT) {
-    double acc[RT][NS];
-#pragma unroll
-    for (int r = 0; r < RT; r++)
-#pragma unroll
-      for (int q = 0; q < NS; q++) acc[r][q] = 0.;
-    for (int d0 = 0; d0 < d; d0 += KE_DC) {
-      const int dc = min(KE_DC, d - d0);
-      __syncthreads();
-      // (test points past m and training points past n read the last one; their results are dropped)
-      for (int e = tid; e < PR_T * dc; e += PR_T) {
-        const int pt = e / dc, j = e % dc;
-        xt[pt * (KE_DC + 1) + j] = hssk_gload(T, (size_t)min(cb + pt, m - 1) * d + d0 + j);
-      }
-      for (int e = tid; e < RT * dc; e += PR_T) {
-        const int pt = e / dc, j = e % dc;
-        xr[pt * KE_DC + j] = hssk_gload(ks.X, (size_t)min(r0 + pt, ks.n - 1) * d + d0 + j);
-      }
-      if (d0 == 0 && tid < RT) wr[tid] = r0 + tid < ks.n ? w[r0 + tid] : 0.;
-      __syncthreads();
-      for (int j = 0; j < dc; j++) {
-        const double t = xt[tid * (KE_DC + 1) + j];
-#pragma unroll
-        for (int r = 0; r < RT; r++) {
-          const double df = xr[r * KE_DC + j] - t;
-          if (TYPE == 2) {
-            const double tmp = exp(-(df * df) / h2);
-            double pw = tmp;
-#pragma unroll
-            for (int q = 0; q < NS; q++)
-              if (q < P) { acc[r][q] += pw; pw *= tmp; }
-          } else {
-            acc[r][0] += TYPE == 0 ? df * df : fabs(df);
-          }
-        }
-      }
-    }
-    const int rend = (int)min((long long)RT, ks.n - r0);
-#pragma unroll
-    for (int r = 0; r < RT; r++)
-      if (r < rend) {
-        double v = 0.;
-        if (TYPE == 2) {
-          double S[8], Kpp[9];
-#pragma unroll
-          for (int q = 0; q < 8; q++) S[q] = acc[r][q < NS ? q : 0];
-          anova_newton<8>(S, Kpp, P, v);
-        } else {
-          v = exp(acc[r][0] * (TYPE == 0 ? -1. / h2 : -1. / ks.h));
-        }
-        sum += wr[r] * v;
-      }
-  }
-  if (c < m) pred[c] = sum;
-}
-
-void check_spec(const hssk_kernel_spec& ks) {
-  if (ks.type < 0 || ks.type > 2) throw std::invalid_argument("hssk kernel: type must be 0 (Gauss), 1 (Laplace) or 2 (ANOVA)");
-  if (ks.d <= 0 || ks.n < 0 || !ks.X) throw std::invalid_argument("hssk kernel: bad point set");
-  if (ks.type == 2 && (ks.p < 1 || ks.p > 8 || ks.p > ks.d)) throw std::invalid_argument("hssk kernel: ANOVA degree must be in [1, min(8, d)]");
 }
 
 }  // namespace
@@ -1206,10 +1060,11 @@ extern "C" int hssk_kernel_predict(hssk_ctx* ctx, const hssk_kernel_spec* spec, 
   if (m <= 0) return 0;
   check_spec(*spec);
   const dim3 grid((unsigned)((m + PR_T - 1) / PR_T));
-  if (spec->d <= KNN_DMAX) HSSK_LAUNCH(kernel_predict_kernel, grid, dim3(PR_T), 0, ctx->stream, *spec, w, T, m, pred);
-  else if (spec->type == 0) HSSK_LAUNCH((kernel_predict_wide_kernel<0, 32>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, T, m, pred);
-  else if (spec->type == 1) HSSK_LAUNCH((kernel_predict_wide_kernel<1, 32>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, T, m, pred);
-  else HSSK_LAUNCH((kernel_predict_wide_kernel<2, 8>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, T, m, pred);
+  const size_t z = 0;
+  if (spec->d <= PR_DMAX) HSSK_LAUNCH((kernel_predict_kernel<PR_SUM>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);
+  else if (spec->type == 0) HSSK_LAUNCH((kernel_predict_wide_kernel<0, 32, PR_SUM>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);
+  else if (spec->type == 1) HSSK_LAUNCH((kernel_predict_wide_kernel<1, 32, PR_SUM>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);
+  else HSSK_LAUNCH((kernel_predict_wide_kernel<2, 8, PR_SUM>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);
   hssk_rt::check_launch();
   HSSK_API_END
 }

@@ -145,6 +145,10 @@ class ShiftDesc(C.Structure):
     _fields_ = [("A", C.c_void_p), ("n", C.c_int), ("lda", C.c_int)]
 
 
+class LogdetDesc(C.Structure):
+    _fields_ = [("A", C.c_void_p), ("n", C.c_int), ("lda", C.c_int)]
+
+
 class Gen(C.Structure):
     """hssk_gen: a matrix given by a formula (kind 1: Toeplitz 1/(1+|i-j|), 2: its upper triangle)"""
     _fields_ = [("kind", C.c_int), ("reserved", C.c_int), ("p", C.c_double * 4)]
@@ -166,6 +170,7 @@ HSSK_SYMBOLS = [
     "hssk_cluster_median", "hssk_pchol_id_vbatched", "hssk_pchol_id_max_m", "hssk_pchol_id_rank_cap", "hssk_sum_partials", "hssk_gram_vbatched", "hssk_gram_gen_vbatched", "hssk_gram_gen_supported",
     "hssk_sgemm_sketch", "hssk_narrow_f32", "hssk_gather_elems_f32",
     "hssk_kernel_predict_f32", "hssk_kernel_predict_f32_wide", "hssk_kernel_predict_splits",
+    "hssk_logabsdet_vbatched", "hssk_kernel_cross", "hssk_kernel_predict_cols",
 ]
 
 
@@ -285,6 +290,9 @@ class Hssk:
             getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_double,
                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.hssk_kernel_predict_splits.argtypes = [C.c_longlong, C.c_int]
+        L.hssk_logabsdet_vbatched.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.hssk_kernel_cross.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
+        L.hssk_kernel_predict_cols.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p]
         L.hssk_colsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.hssk_cluster_median.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         for fn in ("hssk_pchol_id_vbatched", "hssk_sum_partials", "hssk_gram_vbatched"):
@@ -344,6 +352,16 @@ class Hssk:
         for a in (dX, dT, dw, dp):
             a.free()
         return (out, st) if stats else out
+
+    def logabsdet(self, blocks):
+        """hssk_logabsdet_vbatched on device blocks [(DevArray, n, lda), ...]: returns (partials, total)"""
+        descs = [LogdetDesc(a.ptr, n, lda) for a, n, lda in blocks]
+        arr = (LogdetDesc * max(len(descs), 1))(*descs)
+        dp = self.empty((len(descs) + 1,))
+        self.check(self.lib.hssk_logabsdet_vbatched(self.ctx, arr, len(descs), dp.at(1), dp.ptr))
+        out = dp.get()
+        dp.free()
+        return out[1:], out[0]
 
     def batch(self, fn_name, descs):
         if not descs:

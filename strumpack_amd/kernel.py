@@ -11,6 +11,9 @@ KERNEL_SYMBOLS = [
     "SPX_clustering", "SPX_clustering_device", "SPX_kernel_node_info", "SPX_kernel_set_neighbors", "SPX_approximate_neighbors",
     "STRUMPACK_create_kernel_float", "STRUMPACK_destroy_kernel_float", "STRUMPACK_kernel_fit_HSS_float",
     "STRUMPACK_kernel_predict_float", "SPX_kernel_predict_device_float", "SPX_kernel_predict_stats",
+    "SPX_kernel_keep_model", "SPX_kernel_logabsdet", "SPX_kernel_log_marginal_likelihood", "SPX_kernel_predict_variance_double",
+    "SPX_kernel_variance_ms", "SPX_kernel_model_set_lambda", "SPX_kernel_model_write", "SPX_kernel_model_labels",
+    "SPX_kernel_model_points",
 ]
 KERNEL_TYPES = {"Gauss": 0, "rbf": 0, "Laplace": 1, "ANOVA": 2}
 CLUSTERING = {"natural": 0, "2means": 1, "kdtree": 2, "pca": 3, "cobble": 4}
@@ -38,6 +41,15 @@ def load(path):
     L.SPX_kernel_node_info.argtypes = [vp, vp, C.c_int]
     L.SPX_kernel_set_neighbors.argtypes = [vp, C.c_int, vp]
     L.SPX_approximate_neighbors.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    L.SPX_kernel_keep_model.argtypes = [vp, C.c_int]
+    L.SPX_kernel_logabsdet.argtypes = [vp, C.POINTER(C.c_double)]
+    L.SPX_kernel_log_marginal_likelihood.argtypes = [vp, C.POINTER(C.c_double)]
+    L.SPX_kernel_predict_variance_double.argtypes = [vp, C.c_int, vp, vp]
+    L.SPX_kernel_variance_ms.argtypes = [vp, vp]
+    L.SPX_kernel_model_set_lambda.argtypes = [vp, C.c_double]
+    L.SPX_kernel_model_write.argtypes = [vp, C.c_char_p]
+    L.SPX_kernel_model_labels.argtypes = [vp, vp]
+    L.SPX_kernel_model_points.argtypes = [vp, vp]
     L.SPX_clustering.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int]
     L.SPX_clustering_device.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
     return L
@@ -46,9 +58,11 @@ def load(path):
 class KernelRegression:
     """Kernel ridge regression classifier, same shape as the reference's STRUMPACKKernel (fit / predict)."""
 
-    def __init__(self, lib, h=1.0, lam=4.0, kernel="rbf", degree=1, argv=()):
+    def __init__(self, lib, h=1.0, lam=4.0, kernel="rbf", degree=1, argv=(), keep_model=False):
+        """keep_model (double fits only): the fit keeps its factored matrix, so that logabsdet, log_marginal_likelihood,
+        predict_variance, set_lambda and write_model work afterwards"""
         self.L, self.h, self.lam, self.ktype, self.p, self.argv = lib, h, lam, KERNEL_TYPES[kernel], degree, list(argv)
-        self.K, self.dtype = None, np.dtype(np.float64)
+        self.K, self.dtype, self.keep_model = None, np.dtype(np.float64), bool(keep_model)
 
     def fit(self, X, y, neighbors=None):
         """float32 X: the float entry points (promoted fit, FP32 prediction; the fit works on a copy of X, kept in cluster
@@ -66,10 +80,65 @@ class KernelRegression:
         if neighbors is not None:   # tests: k x n lists in cluster order (see include/kernel/Kernel.h)
             nb = np.ascontiguousarray(neighbors, dtype=np.int32)
             self.L.SPX_kernel_set_neighbors(self.K, nb.shape[1], nb.ctypes.data)
+        if self.keep_model and self.L.SPX_kernel_keep_model(self.K, 1):
+            raise RuntimeError("SPX_kernel_keep_model failed (a double fit with a built-in kernel is needed)")
         args = [b"kernel"] + [a.encode() for a in self.argv]
         argv = (C.c_char_p * len(args))(*args)
         getattr(self.L, "STRUMPACK_kernel_fit_HSS_" + sfx)(self.K, y.ctypes.data, len(args), argv)
         return self
+
+    # ---- the kept model (keep_model=True) ----
+    def logabsdet(self):
+        """log|det H| of the compressed K + lambda I"""
+        out = C.c_double(0.0)
+        if self.L.SPX_kernel_logabsdet(self.K, C.byref(out)):
+            raise RuntimeError("SPX_kernel_logabsdet failed (no kept model)")
+        return out.value
+
+    def log_marginal_likelihood(self):
+        out = C.c_double(0.0)
+        if self.L.SPX_kernel_log_marginal_likelihood(self.K, C.byref(out)):
+            raise RuntimeError("SPX_kernel_log_marginal_likelihood failed (no kept model)")
+        return out.value
+
+    def predict_variance(self, T):
+        """variance of the latent function at the rows of T (add lam for the observation noise); not clamped: the compressed
+        matrix is K + lam I only up to the compression tolerance, so a value may be slightly negative"""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        out = np.zeros(T.shape[0])
+        if self.L.SPX_kernel_predict_variance_double(self.K, T.shape[0], T.ctypes.data, out.ctypes.data):
+            raise RuntimeError("SPX_kernel_predict_variance_double failed (no kept model)")
+        return out
+
+    def variance_ms(self):
+        out = np.zeros(3)
+        if self.L.SPX_kernel_variance_ms(self.K, out.ctypes.data):
+            raise RuntimeError("no kept model")
+        return dict(zip(["cross_ms", "solve_ms", "colsum_ms"], out.tolist()))
+
+    def set_lambda(self, lam):
+        """a new lambda on the kept compression: shift, factor, solve; weights() and the predictions follow"""
+        if self.L.SPX_kernel_model_set_lambda(self.K, float(lam)):
+            raise RuntimeError("SPX_kernel_model_set_lambda failed (no kept model)")
+        self.lam = float(lam)
+        return self
+
+    def write_model(self, path):
+        if self.L.SPX_kernel_model_write(self.K, str(path).encode()):
+            raise RuntimeError("SPX_kernel_model_write failed (no kept model)")
+
+    def model_labels(self):
+        y = np.zeros(self.n)
+        if self.L.SPX_kernel_model_labels(self.K, y.ctypes.data):
+            raise RuntimeError("no kept model")
+        return y
+
+    def model_points(self):
+        """the training points in cluster order (n x d)"""
+        X = np.zeros((self.n, self.d))
+        if self.L.SPX_kernel_model_points(self.K, X.ctypes.data):
+            raise RuntimeError("no kept model")
+        return X
 
     def decision_function(self, T):
         """T: m x d array; after a float32 fit also a float32 torch tensor on the device (m x d, contiguous), which is
