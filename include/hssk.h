@@ -849,6 +849,21 @@ typedef struct hssk_logdet_desc {
   int n, lda;
 } hssk_logdet_desc;
 int hssk_logabsdet_vbatched(hssk_ctx* ctx, const hssk_logdet_desc* descs, int count, double* partial, double* out);
+/* out(i, c) = sum_r g(x_i, x_r) B(r, c), i, r < n over the spec's own points, c < nc, 1 <= nc <= 64: the product of the EXACT
+ * kernel matrix with a block of vectors, the matrix never stored.  B and out: device, column-major, ldb, ldo >= n, out may not
+ * alias B; the rows n .. ldo - 1 of out are not touched.  deriv = 0: g = k, spec->lambda added on the diagonal (the product with
+ * K + lambda I); deriv = 1: g = dk/dh = k |x - y|_2^2 / h^3 (Gauss), k |x - y|_1 / h^2 (Laplace), the diagonal exactly 0.  Gauss
+ * and Laplace, any d >= 1 (beyond 64 coordinates the points pass through the LDS 32 coordinates at a time); ANOVA returns
+ * HSSK_UNSUPPORTED.  The grid is (tiles of 64 rows) x (splits of the training points): splits = 0 takes
+ * hssk_kernel_matmul_splits(n), a positive value forces the count (at most one split per 16 training points).  Split partials
+ * go to slabs the context keeps and are added in split order (hssk_sum_slabs): no atomics, bitwise repeatable.  n = 0 or nc = 0:
+ * nothing to do. */
+int hssk_kernel_matmul(hssk_ctx* ctx, const hssk_kernel_spec* spec, int deriv, const double* B, long long ldb, int nc, double* out,
+                       long long ldo, int splits);
+int hssk_kernel_matmul_splits(long long n);   /* what splits = 0 chooses: a function of n alone */
+/* out[c] = sum_{i < n} A(i, c) B(i, c), c < nc (A, B: device, column-major, lda, ldb >= n; out: device, nc doubles).  One
+ * workgroup per column, fixed summation order, no atomics: bitwise repeatable. */
+int hssk_coldots(hssk_ctx* ctx, const double* A, long long lda, const double* B, long long ldb, long long n, int nc, double* out);
 /* peak-rate probe: runs a dependent-free v_mfma_f64_16x16x4_f64 loop on every CU and returns the
  * measured TFLOP/s (used by bench.py to confirm the FP64 matrix roof on the box) */
 double hssk_mfma_f64_peak_tflops(hssk_ctx* ctx, int iters);

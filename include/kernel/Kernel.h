@@ -78,6 +78,20 @@ int SPX_kernel_model_write(STRUMPACKKernel K, const char* path);
 /* the kept labels (n doubles) and the training points (d x n), both in cluster order */
 int SPX_kernel_model_labels(STRUMPACKKernel K, double* y);
 int SPX_kernel_model_points(STRUMPACKKernel K, double* x);
+/* The gradient of the log marginal likelihood L in the width h and in lambda (Gauss and Laplace):
+ *   grad[0] = dL/dh = 1/2 alpha^T K' alpha - 1/2 tr(H^-1 K'),   grad[1] = dL/dlambda = 1/2 alpha^T alpha - 1/2 tr(H^-1),
+ * K' = dK/dh the EXACT kernel derivative, H^-1 the kept, compressed and factored matrix, the traces estimated with the m >= 1
+ * probe vectors z_k as the mean of s_k^T K' z_k and s_k^T z_k, s_k = H^-1 z_k.  Z: n x m column-major, rows in cluster order
+ * (as SPX_kernel_model_points); NULL: the Rademacher block SPX_kernel_model_probes(m, seed) gives.  terms: NULL or 4 + 2 m
+ * doubles: quad_h = 1/2 alpha^T K' alpha, quad_lambda = 1/2 alpha^T alpha, trace_h, trace_lambda (the means), then the m values
+ * s_k^T K' z_k and the m values s_k^T z_k.  Non-zero also for an ANOVA kernel and for m < 1. */
+int SPX_kernel_lml_gradient(STRUMPACKKernel K, int m, const double* Z, unsigned long long seed, double grad[2], double* terms);
+/* the n x m block of +-1 entries the seeded form uses: std::mt19937_64(seed), one bit per entry, column by column */
+int SPX_kernel_model_probes(STRUMPACKKernel K, int m, unsigned long long seed, double* Z);
+/* *out = ||y - (K + lambda I) alpha||_2 / ||y||_2 with the EXACT kernel matrix: how far the compressed fit is from the exact one */
+int SPX_kernel_model_residual(STRUMPACKKernel K, double* out);
+/* device-clock milliseconds of the last gradient call: out[0] kernel products, [1] solves, [2] column dot products */
+int SPX_kernel_gradient_ms(STRUMPACKKernel K, double* out);
 /* binary_tree_clustering on its own (clustering/Clustering.hpp:143-168): algo 0 natural, 1 2means, 2 kdtree,
  * 3 pca, 4 cobble; data (d x n) is reordered in place, perm is 1-based; returns the number of leaves and writes
  * at most cap leaf sizes */

@@ -4,6 +4,7 @@
 
 #include <chrono>
 #include <cstdlib>
+#include <random>
 
 #include "DevicePool.hpp"
 #include "HSSMatrix.hpp"
@@ -118,6 +119,107 @@ std::vector<double> Kernel<double>::predict_variance(const DenseMatrix<double>& 
   for (int w = 0; w < 3; w++) var_ms_[w] = hssk_watch_read_ms(ctx, w + 1, nullptr);
   for (int c = 0; c < m; c++) var[c] = ktt[c] - quad[c];
   return var;
+}
+
+// ---- gradient of the log marginal likelihood, residual of the fit against the exact kernel matrix -------------
+namespace {
+struct GradBuf {   // a device pool chunk for the length of a call
+  void* p = nullptr; size_t bytes; hssk_ctx* ctx;
+  GradBuf(hssk_ctx* c, size_t b) : bytes(std::max<size_t>(b, 256)), ctx(c) { p = DevicePool::get().acquire(bytes); if (!p) throw std::runtime_error(hssk_last_error()); }
+  ~GradBuf() { hssk_sync(ctx); DevicePool::get().release(p, bytes); }
+};
+}  // namespace
+
+DenseMatrix<double> Kernel<double>::model_probes(int m, unsigned long long seed) const {
+  model("model_probes");
+  if (m < 1) throw std::invalid_argument("model_probes: at least one probe vector");
+  DenseMatrix<double> Z(n(), m);
+  std::mt19937_64 gen(seed);
+  for (int c = 0; c < m; c++) {
+    unsigned long long word = 0;
+    for (std::size_t i = 0; i < n(); i++) {
+      if (i % 64 == 0) word = gen();
+      Z(i, c) = ((word >> (i % 64)) & 1ULL) ? 1. : -1.;
+    }
+  }
+  return Z;
+}
+
+LmlGradient Kernel<double>::log_marginal_likelihood_gradient(int m, unsigned long long seed) const {
+  model("log_marginal_likelihood_gradient");
+  if (m < 1) throw std::invalid_argument("log_marginal_likelihood_gradient: at least one probe vector");
+  return log_marginal_likelihood_gradient(model_probes(m, seed));
+}
+
+LmlGradient Kernel<double>::log_marginal_likelihood_gradient(const DenseMatrix<double>& Z) const {
+  const Model& M = model("log_marginal_likelihood_gradient");
+  if (device_type() != 0 && device_type() != 1) throw std::invalid_argument("log_marginal_likelihood_gradient: Gauss and Laplace kernels only");
+  if (Z.cols() < 1) throw std::invalid_argument("log_marginal_likelihood_gradient: at least one probe vector");
+  if (Z.rows() != n()) throw std::invalid_argument("log_marginal_likelihood_gradient: one probe row per training point expected (cluster order)");
+  const int m = int(Z.cols()), dim = int(d()), CH = 64;
+  const long long nn = (long long)n();
+  hssk_ctx* ctx = M.ctx();
+  grad_ms_[0] = grad_ms_[1] = grad_ms_[2] = 0.;
+  // B: alpha | the probes, S = H^-1 B, G = K' B; the dots of a block: [0, 64) S.G, [64, 128) S.B, [128] alpha.G(:, 0)
+  GradBuf bB(ctx, sizeof(double) * nn * CH), bS(ctx, sizeof(double) * nn * CH), bG(ctx, sizeof(double) * nn * CH), bD(ctx, sizeof(double) * (2 * CH + 1));
+  double *dB = (double*)bB.p, *dS = (double*)bS.p, *dG = (double*)bG.p, *dD = (double*)bD.p;
+  const hssk_kernel_spec spec{M.dX, nn, dim, device_type(), degree(), width(), 0.};
+  LmlGradient g;
+  g.th.assign(m, 0.);
+  g.tl.assign(m, 0.);
+  std::vector<double> dots(2 * CH + 1, 0.);
+  double aga = 0.;
+  for (int c0 = 0; c0 < m + 1; c0 += CH) {   // column c of alpha | Z
+    const int nc = std::min(CH, m + 1 - c0), lead = c0 == 0 ? 1 : 0, z0 = c0 == 0 ? 0 : c0 - 1, nz = nc - lead;
+    if (lead) ckk(hssk_memcpy_h2d(ctx, dB, M.weights.data(), (long long)sizeof(double) * nn));
+    if (nz > 0) ckk(hssk_memcpy2d_h2d(ctx, dB + (size_t)lead * nn, sizeof(double) * nn, Z.ptr(0, z0), sizeof(double) * Z.ld(), sizeof(double) * nn, nz));
+    ckk(hssk_memcpy_d2d(ctx, dS, dB, (long long)sizeof(double) * nn * nc));
+    hssk_watch_start(ctx, 2);
+    M.H.solve_device(nc, dS, nn);   // (the same buffer for every block: the recorded sweep is replayed)
+    hssk_watch_stop(ctx, 2);
+    hssk_watch_start(ctx, 1);
+    ckk(hssk_kernel_matmul(ctx, &spec, 1, dB, nn, nc, dG, nn, 0));
+    hssk_watch_stop(ctx, 1);
+    hssk_watch_start(ctx, 3);
+    ckk(hssk_coldots(ctx, dS, nn, dG, nn, nn, nc, dD));
+    ckk(hssk_coldots(ctx, dS, nn, dB, nn, nn, nc, dD + CH));
+    if (lead) ckk(hssk_coldots(ctx, dB, nn, dG, nn, nn, 1, dD + 2 * CH));
+    hssk_watch_stop(ctx, 3);
+    ckk(hssk_memcpy_d2h(ctx, dots.data(), dD, (long long)sizeof(double) * (2 * CH + 1)));
+    for (int c = lead; c < nc; c++) { g.th[z0 + c - lead] = dots[c]; g.tl[z0 + c - lead] = dots[CH + c]; }
+    if (lead) aga = dots[2 * CH];
+  }
+  for (int w = 0; w < 3; w++) grad_ms_[w] = hssk_watch_read_ms(ctx, w + 1, nullptr);
+  long double aa = 0.L, sh = 0.L, sl = 0.L;
+  for (long long i = 0; i < nn; i++) aa += (long double)M.weights(i, 0) * (long double)M.weights(i, 0);
+  for (int k = 0; k < m; k++) { sh += (long double)g.th[k]; sl += (long double)g.tl[k]; }
+  g.quad_h = 0.5 * aga;
+  g.quad_lambda = (double)(0.5L * aa);
+  g.trace_h = (double)(sh / m);
+  g.trace_lambda = (double)(sl / m);
+  g.dh = g.quad_h - 0.5 * g.trace_h;
+  g.dlambda = g.quad_lambda - 0.5 * g.trace_lambda;
+  return g;
+}
+
+double Kernel<double>::model_residual() const {
+  const Model& M = model("model_residual");
+  if (device_type() != 0 && device_type() != 1) throw std::invalid_argument("model_residual: Gauss and Laplace kernels only");
+  const long long nn = (long long)n();
+  hssk_ctx* ctx = M.ctx();
+  GradBuf bB(ctx, sizeof(double) * nn), bG(ctx, sizeof(double) * nn);
+  const hssk_kernel_spec spec{M.dX, nn, int(d()), device_type(), degree(), width(), lambda_};
+  ckk(hssk_memcpy_h2d(ctx, bB.p, M.weights.data(), (long long)sizeof(double) * nn));
+  ckk(hssk_kernel_matmul(ctx, &spec, 0, (const double*)bB.p, nn, 1, (double*)bG.p, nn, 0));
+  std::vector<double> r(nn, 0.);
+  ckk(hssk_memcpy_d2h(ctx, r.data(), bG.p, (long long)sizeof(double) * nn));
+  long double num = 0.L, den = 0.L;
+  for (long long i = 0; i < nn; i++) {
+    const long double e = (long double)M.labels[i] - (long double)r[i];
+    num += e * e;
+    den += (long double)M.labels[i] * (long double)M.labels[i];
+  }
+  return (double)std::sqrt(num / den);
 }
 
 DenseMatrix<double> Kernel<double>::fit_HSS(std::vector<double>& labels, const HSS::HSSOptions<double>& opts) {
@@ -656,6 +758,47 @@ int SPX_kernel_model_points(STRUMPACKKernel K, double* x) {
     for (std::size_t i = 0; i < k->n(); i++) std::copy(k->data().ptr(0, i), k->data().ptr(0, i) + k->d(), x + i * k->d());
     return 0;
   } catch (const std::exception& e) { report(e); return 1; }
+}
+
+int SPX_kernel_lml_gradient(STRUMPACKKernel K, int m, const double* Z, unsigned long long seed, double grad[2], double* terms) {
+  try {
+    auto k = model_of(K);
+    if (!k || m < 1 || !grad) return 1;
+    const kernel::LmlGradient g = Z ? k->log_marginal_likelihood_gradient(DenseMatrix<double>(k->n(), m, Z, k->n()))
+                                    : k->log_marginal_likelihood_gradient(m, seed);
+    grad[0] = g.dh;
+    grad[1] = g.dlambda;
+    if (terms) {
+      terms[0] = g.quad_h; terms[1] = g.quad_lambda; terms[2] = g.trace_h; terms[3] = g.trace_lambda;
+      std::copy(g.th.begin(), g.th.end(), terms + 4);
+      std::copy(g.tl.begin(), g.tl.end(), terms + 4 + m);
+    }
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_model_probes(STRUMPACKKernel K, int m, unsigned long long seed, double* Z) {
+  try {
+    auto k = model_of(K);
+    if (!k || m < 1 || !Z) return 1;
+    const DenseMatrix<double> P = k->model_probes(m, seed);
+    for (int c = 0; c < m; c++) std::copy(P.ptr(0, c), P.ptr(0, c) + k->n(), Z + (size_t)c * k->n());
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_model_residual(STRUMPACKKernel K, double* out) {
+  try {
+    auto k = model_of(K);
+    if (!k || !out) return 1;
+    const double v = k->model_residual();
+    *out = v;
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_gradient_ms(STRUMPACKKernel K, double* out) {
+  auto k = model_of(K);
+  if (!k || !out) return 1;
+  std::copy(k->gradient_ms(), k->gradient_ms() + 3, out);
+  return 0;
 }
 
 int SPX_clustering(int n, int d, double* data, int algo, int leaf_size, int* perm, int* leaf_sizes, int cap) {

@@ -43,6 +43,14 @@ inline KernelType kernel_type(const std::string& k) {
 
 template <typename scalar_t> class Kernel;
 
+// what Kernel<double>::log_marginal_likelihood_gradient returns
+struct LmlGradient {
+  double dh = 0., dlambda = 0.;               // the gradient
+  double quad_h = 0., quad_lambda = 0.;       // 1/2 alpha^T dK/dh alpha, 1/2 alpha^T alpha
+  double trace_h = 0., trace_lambda = 0.;     // means of the per-probe values
+  std::vector<double> th, tl;                 // per probe: s_k^T (dK/dh z_k), s_k^T z_k
+};
+
 template <> class Kernel<double> {
   using scalar_t = double;
   using DenseM_t = DenseMatrix<double>;
@@ -94,6 +102,22 @@ template <> class Kernel<double> {
   const DenseM_t& model_weights() const;
   // device-clock milliseconds of the last predict_variance: cross-kernel blocks, solves, column sums (profiling)
   const double* variance_ms() const { return var_ms_; }
+  // The gradient of the log marginal likelihood in h and lambda (Gauss and Laplace):
+  //   dL/dh = 1/2 alpha^T K' alpha - 1/2 tr(H^-1 K'),   dL/dlambda = 1/2 alpha^T alpha - 1/2 tr(H^-1),
+  // K' = dK/dh the EXACT kernel derivative (hssk_kernel_matmul, never stored), H^-1 the kept, compressed and factored matrix:
+  // the gradient of the exact-kernel likelihood evaluated with the compressed inverse, biased at a loose compression tolerance.
+  // The traces are estimated with the columns z_k of Z (n x m, m >= 1, rows in the model's cluster order) as the mean of
+  // s_k^T K' z_k and s_k^T z_k, s_k = H^-1 z_k: exact for the n probes sqrt(n) e_k, unbiased for Rademacher probes.  Columns go
+  // in blocks of 64 with alpha as one column of the first, so 63 probes cost one pass over the pairs.
+  LmlGradient log_marginal_likelihood_gradient(const DenseM_t& Z) const;
+  // the same with the Rademacher block model_probes(m, seed)
+  LmlGradient log_marginal_likelihood_gradient(int m = 63, unsigned long long seed = 0) const;
+  // n x m entries +-1 from std::mt19937_64(seed), one bit per entry, column by column
+  DenseM_t model_probes(int m, unsigned long long seed) const;
+  // ||y - (K + lambda I) alpha||_2 / ||y||_2 with the EXACT kernel matrix (one product; the norms in long double)
+  scalar_t model_residual() const;
+  // device-clock milliseconds of the last gradient call: kernel products, solves, column dot products (profiling)
+  const double* gradient_ms() const { return grad_ms_; }
 
   const DenseM_t& data() const { return data_; }
   DenseM_t& data() { return data_; }
@@ -125,6 +149,7 @@ template <> class Kernel<double> {
   std::unique_ptr<Model> model_;
   bool keep_model_ = false;
   mutable double var_ms_[3] = {0., 0., 0.};
+  mutable double grad_ms_[3] = {0., 0., 0.};
   const Model& model(const char* what) const;
 };
 

@@ -145,6 +145,19 @@ struct hssk_ctx {
     }
     return d_gen;
   }
+  // split partials of hssk_kernel_matmul: a buffer of its own, so that growing it never frees what a recorded sweep still names
+  double* d_kmm = nullptr;
+  size_t kmm_bytes = 0;
+  double* kmm_slabs(size_t bytes) {
+    if (bytes > kmm_bytes) {
+      sync_all();
+      hssk_rt::dev_free(d_kmm);
+      d_kmm = nullptr; kmm_bytes = 0;
+      d_kmm = (double*)hssk_rt::dev_malloc(bytes);
+      kmm_bytes = bytes;
+    }
+    return d_kmm;
+  }
   double* scratch(size_t bytes) {
     if (bytes > scratch_bytes) {
       sync_all();

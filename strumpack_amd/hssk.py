@@ -171,6 +171,7 @@ HSSK_SYMBOLS = [
     "hssk_sgemm_sketch", "hssk_narrow_f32", "hssk_gather_elems_f32",
     "hssk_kernel_predict_f32", "hssk_kernel_predict_f32_wide", "hssk_kernel_predict_splits",
     "hssk_logabsdet_vbatched", "hssk_kernel_cross", "hssk_kernel_predict_cols",
+    "hssk_kernel_matmul", "hssk_kernel_matmul_splits", "hssk_coldots",
 ]
 
 
@@ -293,6 +294,10 @@ class Hssk:
         L.hssk_logabsdet_vbatched.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.hssk_kernel_cross.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
         L.hssk_kernel_predict_cols.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p]
+        L.hssk_kernel_matmul.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong,
+                                         C.c_int]
+        L.hssk_kernel_matmul_splits.argtypes = [C.c_longlong]
+        L.hssk_coldots.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p]
         L.hssk_colsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.hssk_cluster_median.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         for fn in ("hssk_pchol_id_vbatched", "hssk_sum_partials", "hssk_gram_vbatched"):

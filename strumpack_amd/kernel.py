@@ -13,7 +13,8 @@ KERNEL_SYMBOLS = [
     "STRUMPACK_kernel_predict_float", "SPX_kernel_predict_device_float", "SPX_kernel_predict_stats",
     "SPX_kernel_keep_model", "SPX_kernel_logabsdet", "SPX_kernel_log_marginal_likelihood", "SPX_kernel_predict_variance_double",
     "SPX_kernel_variance_ms", "SPX_kernel_model_set_lambda", "SPX_kernel_model_write", "SPX_kernel_model_labels",
-    "SPX_kernel_model_points",
+    "SPX_kernel_model_points", "SPX_kernel_lml_gradient", "SPX_kernel_model_probes", "SPX_kernel_model_residual",
+    "SPX_kernel_gradient_ms",
 ]
 KERNEL_TYPES = {"Gauss": 0, "rbf": 0, "Laplace": 1, "ANOVA": 2}
 CLUSTERING = {"natural": 0, "2means": 1, "kdtree": 2, "pca": 3, "cobble": 4}
@@ -50,6 +51,10 @@ def load(path):
     L.SPX_kernel_model_write.argtypes = [vp, C.c_char_p]
     L.SPX_kernel_model_labels.argtypes = [vp, vp]
     L.SPX_kernel_model_points.argtypes = [vp, vp]
+    L.SPX_kernel_lml_gradient.argtypes = [vp, C.c_int, vp, C.c_ulonglong, vp, vp]
+    L.SPX_kernel_model_probes.argtypes = [vp, C.c_int, C.c_ulonglong, vp]
+    L.SPX_kernel_model_residual.argtypes = [vp, C.POINTER(C.c_double)]
+    L.SPX_kernel_gradient_ms.argtypes = [vp, vp]
     L.SPX_clustering.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int]
     L.SPX_clustering_device.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
     return L
@@ -139,6 +144,48 @@ class KernelRegression:
         if self.L.SPX_kernel_model_points(self.K, X.ctypes.data):
             raise RuntimeError("no kept model")
         return X
+
+    def model_probes(self, m, seed=0):
+        """the n x m block of +-1 probes the seeded gradient uses (rows in cluster order)"""
+        Z = np.zeros((self.n, int(m)), order="F")
+        if self.L.SPX_kernel_model_probes(self.K, int(m), int(seed), Z.ctypes.data):
+            raise RuntimeError("SPX_kernel_model_probes failed (no kept model, or m < 1)")
+        return Z
+
+    def log_marginal_likelihood_gradient(self, probes=63, seed=0, Z=None, terms=False):
+        """(dL/dh, dL/dlambda) of the log marginal likelihood: the exact kernel derivative against the kept, compressed inverse,
+        the traces estimated with `probes` Rademacher vectors from `seed`, or with the columns of Z (n x m, rows in cluster order:
+        the order of model_points()).  terms=True: also a dict with quad_h, quad_lambda, trace_h, trace_lambda and the per-probe
+        values th, tl (their spread gives the standard error of the trace estimates)."""
+        if Z is not None:
+            Z = np.asfortranarray(Z, dtype=np.float64)
+            if Z.ndim != 2 or Z.shape[0] != self.n or Z.shape[1] < 1:
+                raise ValueError("log_marginal_likelihood_gradient: Z must be n x m with m >= 1")
+            m, zp = Z.shape[1], Z.ctypes.data
+        else:
+            m, zp = int(probes), None
+        if m < 1:
+            raise ValueError("log_marginal_likelihood_gradient: at least one probe vector")
+        grad, t = np.zeros(2), np.zeros(4 + 2 * m)
+        if self.L.SPX_kernel_lml_gradient(self.K, m, zp, int(seed), grad.ctypes.data, t.ctypes.data):
+            raise RuntimeError("SPX_kernel_lml_gradient failed (a kept model of a Gauss or Laplace fit is needed)")
+        if not terms:
+            return float(grad[0]), float(grad[1])
+        return float(grad[0]), float(grad[1]), dict(quad_h=t[0], quad_lambda=t[1], trace_h=t[2], trace_lambda=t[3],
+                                                    th=t[4:4 + m].copy(), tl=t[4 + m:].copy())
+
+    def gradient_ms(self):
+        out = np.zeros(3)
+        if self.L.SPX_kernel_gradient_ms(self.K, out.ctypes.data):
+            raise RuntimeError("no kept model")
+        return dict(zip(["product_ms", "solve_ms", "dots_ms"], out.tolist()))
+
+    def fit_residual(self):
+        """||y - (K + lam I) alpha|| / ||y|| with the EXACT kernel matrix: how far the compressed fit is from the exact one"""
+        out = C.c_double(0.0)
+        if self.L.SPX_kernel_model_residual(self.K, C.byref(out)):
+            raise RuntimeError("SPX_kernel_model_residual failed (a kept model of a Gauss or Laplace fit is needed)")
+        return out.value
 
     def decision_function(self, T):
         """T: m x d array; after a float32 fit also a float32 torch tensor on the device (m x d, contiguous), which is
