@@ -864,6 +864,28 @@ int hssk_kernel_matmul_splits(long long n);   /* what splits = 0 chooses: a func
 /* out[c] = sum_{i < n} A(i, c) B(i, c), c < nc (A, B: device, column-major, lda, ldb >= n; out: device, nc doubles).  One
  * workgroup per column, fixed summation order, no atomics: bitwise repeatable. */
 int hssk_coldots(hssk_ctx* ctx, const double* A, long long lda, const double* B, long long ldb, long long n, int nc, double* out);
+/* ---- vector kernels of a block Krylov iteration: up to 64 right-hand sides in lockstep (kernels/hssk_krylov.hip) -------------
+ * A basis is a sequence of blocks: block j is n x nc column-major with leading dimension ldv >= n at V + j ldv nc, so that a block
+ * can be handed to hssk_kernel_matmul or to a device solve as it is.  Column c of the blocks is the basis of right-hand side c;
+ * the columns never mix.  1 <= nc <= 64; n = 0 or nc = 0: nothing to do.  nc > 64, a leading dimension below n, a null pointer
+ * or a negative k / kcount is refused (non-zero) with the outputs untouched.  Rows n .. ld - 1 and columns >= nc are never
+ * written.  Every sum has a fixed order (one row per thread, lanes, waves, row chunks), no atomics: bitwise repeatable, and the
+ * result of a column does not depend on its neighbours.
+ * hssk_krylov_start: per column r = b - ax, norms[c] = ||r||_2 (device, nc doubles), V0(:, c) = r / ||r||, zeros where the norm
+ * is 0. */
+int hssk_krylov_start(hssk_ctx* ctx, const double* B, long long ldb, const double* AX, long long ldax, long long n, int nc,
+                      double* V0, long long ldv, double* norms);
+/* Per column c whose bit of `active` is set: W(:, c) is orthogonalised against V_0 .. V_k (:, c) by classical Gram-Schmidt
+ * applied twice; Hout(j, c), j <= k, is the sum of the two passes' coefficients, Hout(k + 1, c) = ||w||_2 after the second pass,
+ * block k + 1 receives w / ||w|| (zeros if the norm is 0), and W(:, c) is left holding the orthogonalised, not normalised w.
+ * An inactive column: zeros in block k + 1 and in Hout(0 .. k + 1, c), W(:, c) untouched.  Hout: device, ldh >= k + 2. */
+int hssk_krylov_orth(hssk_ctx* ctx, double* V, long long ldv, long long n, int nc, int k, double* W, long long ldw,
+                     unsigned long long active, double* Hout, long long ldh);
+/* out(:, c) = sum_{j < kcount} Y(j, c) V_j(:, c) (accumulate == 0) or out(:, c) += that sum; the terms are added in the order of
+ * j, out last.  Y: device, ldy >= kcount.  kcount = 0: out is zeroed (accumulate == 0) or not touched (accumulate != 0).  out may
+ * not alias the basis. */
+int hssk_krylov_combine(hssk_ctx* ctx, const double* V, long long ldv, long long n, int nc, int kcount, const double* Y,
+                        long long ldy, double* out, long long ldo, int accumulate);
 /* peak-rate probe: runs a dependent-free v_mfma_f64_16x16x4_f64 loop on every CU and returns the
  * measured TFLOP/s (used by bench.py to confirm the FP64 matrix roof on the box) */
 double hssk_mfma_f64_peak_tflops(hssk_ctx* ctx, int iters);

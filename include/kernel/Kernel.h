@@ -92,6 +92,31 @@ int SPX_kernel_model_probes(STRUMPACKKernel K, int m, unsigned long long seed, d
 int SPX_kernel_model_residual(STRUMPACKKernel K, double* out);
 /* device-clock milliseconds of the last gradient call: out[0] kernel products, [1] solves, [2] column dot products */
 int SPX_kernel_gradient_ms(STRUMPACKKernel K, double* out);
+/* ---- solves with the EXACT K + lambda I from the kept model (Gauss and Laplace): right-preconditioned restarted
+ * GMRES on the device, the kept ULV factors as preconditioner, up to 64 columns in lockstep.  A column is converged when its true
+ * residual ||b - (K + lambda I) x||_2 <= rtol ||b||_2; the steps of a call (per block of 64 columns) never exceed maxit; a cycle
+ * has at most `restart` steps.  Not converging is NOT an error: the call returns 0 and info says so.  Non-zero, outputs
+ * untouched and the model undisturbed: no kept model, a float handle, a user-defined or ANOVA kernel, rtol <= 0 or not finite,
+ * maxit < 1, restart < 1, a leading dimension below n.
+ * info: NULL or 8 + 2 m doubles (m the number of columns: 1 for the refine call, the test points for the variance):
+ *   [0] converged (1 / 0: every column), [1] steps of the slowest column, [2] exact products, [3] ULV solves, [4] cycles (summed
+ *   over the blocks), [5] largest relative residual at the start, [6] largest at the end, [7] m, then the m relative residuals
+ *   at the end and the m step counts.
+ * SPX_kernel_model_refine: the kept labels as right-hand side, the current weights as first iterate; the handle's weights become
+ * the last iterate (SPX_kernel_weights, STRUMPACK_kernel_predict_double, SPX_kernel_model_residual and the y^T alpha of the log
+ * marginal likelihood follow; SPX_kernel_logabsdet stays that of the compressed matrix).  SPX_kernel_model_set_lambda and a new
+ * fit replace them by the compressed solve again. */
+int SPX_kernel_model_refine(STRUMPACKKernel K, double rtol, int maxit, int restart, double* info);
+/* X (n x m, ldx) = (K + lambda I)^-1 B (n x m, ldb), rows in cluster order, any m >= 0, from the first iterate H^-1 b; the model is
+ * not changed */
+int SPX_kernel_model_solve(STRUMPACKKernel K, int m, const double* B, int ldb, double* X, int ldx, double rtol, int maxit, int restart,
+                           double* info);
+/* SPX_kernel_predict_variance_double with the exact solve in place of the compressed one; not clamped */
+int SPX_kernel_predict_variance_exact_double(STRUMPACKKernel K, int m, const double* test, double* var, double rtol, int maxit, int restart,
+                                             double* info);
+/* device-clock milliseconds of the last of these three calls: out[0] exact products, [1] ULV solves, [2] Krylov kernels (zeros
+ * before the first one).  Refused like them: no kept model, a float handle, a user-defined or ANOVA kernel. */
+int SPX_kernel_krylov_ms(STRUMPACKKernel K, double out[3]);
 /* binary_tree_clustering on its own (clustering/Clustering.hpp:143-168): algo 0 natural, 1 2means, 2 kdtree,
  * 3 pca, 4 cobble; data (d x n) is reordered in place, perm is 1-based; returns the number of leaves and writes
  * at most cap leaf sizes */

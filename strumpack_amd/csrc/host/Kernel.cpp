@@ -79,9 +79,53 @@ DenseMatrix<double> Kernel<double>::model_set_lambda(double lambda) {
   return w;
 }
 
+namespace {
+struct GradBuf {   // a device pool chunk for the length of a call
+  void* p = nullptr; size_t bytes; hssk_ctx* ctx;
+  GradBuf(hssk_ctx* c, size_t b) : bytes(std::max<size_t>(b, 256)), ctx(c) { p = DevicePool::get().acquire(bytes); if (!p) throw std::runtime_error(hssk_last_error()); }
+  ~GradBuf() { hssk_sync(ctx); DevicePool::get().release(p, bytes); }
+};
+}  // namespace
+
+// the device blocks of a Krylov call, for blocks of at most ncmax columns: restart + 1 basis blocks, Z (what the ULV solve works
+// on: always this buffer, so that its recorded sweep is replayed), W (the product; the residual's A x at the start of a cycle),
+// U (the update), B and X for callers that have none, and the small coefficient arrays
+struct Kernel<double>::KrylovWork {
+  long long n;
+  int ncmax, m;   // m: steps of a cycle = min(restart, maxit)
+  GradBuf bV, bZ, bW, bU, bB, bX, bS;
+  double *V, *Z, *W, *U, *B, *X, *Y, *Hout, *norms, *ones;
+  KrylovWork(hssk_ctx* ctx, long long n_, int ncmax_, int maxit, int restart, bool own_bx)
+      : n(n_), ncmax(ncmax_), m(std::min(restart, maxit)), bV(ctx, sizeof(double) * n_ * ncmax_ * (size_t)(m + 1)), bZ(ctx, sizeof(double) * n_ * ncmax_),
+        bW(ctx, sizeof(double) * n_ * ncmax_), bU(ctx, sizeof(double) * n_ * ncmax_), bB(ctx, sizeof(double) * n_ * ncmax_),
+        bX(ctx, own_bx ? sizeof(double) * n_ * ncmax_ : 0), bS(ctx, sizeof(double) * (size_t)ncmax_ * (2 * m + 4)) {
+    V = (double*)bV.p; Z = (double*)bZ.p; W = (double*)bW.p; U = (double*)bU.p; B = (double*)bB.p; X = (double*)bX.p;
+    Y = (double*)bS.p; Hout = Y + (size_t)ncmax * m; norms = Hout + (size_t)ncmax * (m + 2); ones = norms + ncmax;
+    const std::vector<double> one(ncmax, 1.);
+    ckk(hssk_memcpy_h2d(ctx, ones, one.data(), (long long)sizeof(double) * ncmax));
+  }
+};
+
 std::vector<double> Kernel<double>::predict_variance(const DenseMatrix<double>& test) const {
   const Model& M = model("predict_variance");
   if (test.rows() != d()) throw std::invalid_argument("predict_variance: test points have the wrong dimension");
+  return variance_chunks(M, test, nullptr, 0., 0, 0, nullptr);
+}
+
+std::vector<double> Kernel<double>::predict_variance_exact(const DenseMatrix<double>& test, KrylovInfo* info, double rtol, int maxit, int restart) const {
+  const Model& M = krylov_model("predict_variance_exact", rtol, maxit, restart);
+  if (test.rows() != d()) throw std::invalid_argument("predict_variance_exact: test points have the wrong dimension");
+  KrylovInfo local;
+  if (test.cols() == 0) { if (info) *info = local; return {}; }
+  KrylovWork ws(M.ctx(), (long long)n(), 64, maxit, restart, false);
+  std::vector<double> var = variance_chunks(M, test, &ws, rtol, maxit, restart, &local);
+  krylov_finish(M, local);
+  if (info) *info = local;
+  return var;
+}
+
+std::vector<double> Kernel<double>::variance_chunks(const Model& M, const DenseMatrix<double>& test, KrylovWork* ws, double rtol, int maxit, int restart,
+                                                    KrylovInfo* info) const {
   const int m = int(test.cols()), dim = int(d()), CH = 64;
   const long long nn = (long long)n();
   std::vector<double> var(m, 0.);
@@ -108,9 +152,14 @@ std::vector<double> Kernel<double>::predict_variance(const DenseMatrix<double>& 
     const hssk_kernel_spec self{dTc, (long long)mc, dim, device_type(), degree(), width(), 0.};
     ckk(hssk_kernel_cross(ctx, &self, dTc, mc, dD, mc));
     ckk(hssk_memcpy2d_d2h(ctx, ktt.data() + c0, sizeof(double), dD, sizeof(double) * (mc + 1), sizeof(double), mc));
+    if (ws) ckk(hssk_memcpy_d2d(ctx, ws->B, dK, (long long)sizeof(double) * nn * mc));   // (the right-hand sides of the exact solve)
     hssk_watch_start(ctx, 2);
     M.H.solve_device(mc, dK, nn);
     hssk_watch_stop(ctx, 2);
+    if (ws) {   // from H^-1 k on: the exact solve of the chunk's columns
+      info->solves++;
+      krylov_block(M, *ws, mc, dK, ws->B, rtol, maxit, restart, *info);
+    }
     hssk_watch_start(ctx, 3);
     ckk(hssk_kernel_predict_cols(ctx, &spec, dK, nn, dTc, mc, dP + c0));
     hssk_watch_stop(ctx, 3);
@@ -122,14 +171,6 @@ std::vector<double> Kernel<double>::predict_variance(const DenseMatrix<double>& 
 }
 
 // ---- gradient of the log marginal likelihood, residual of the fit against the exact kernel matrix -------------
-namespace {
-struct GradBuf {   // a device pool chunk for the length of a call
-  void* p = nullptr; size_t bytes; hssk_ctx* ctx;
-  GradBuf(hssk_ctx* c, size_t b) : bytes(std::max<size_t>(b, 256)), ctx(c) { p = DevicePool::get().acquire(bytes); if (!p) throw std::runtime_error(hssk_last_error()); }
-  ~GradBuf() { hssk_sync(ctx); DevicePool::get().release(p, bytes); }
-};
-}  // namespace
-
 DenseMatrix<double> Kernel<double>::model_probes(int m, unsigned long long seed) const {
   model("model_probes");
   if (m < 1) throw std::invalid_argument("model_probes: at least one probe vector");
@@ -220,6 +261,191 @@ double Kernel<double>::model_residual() const {
     den += (long double)M.labels[i] * (long double)M.labels[i];
   }
   return (double)std::sqrt(num / den);
+}
+
+// ---- solves with the exact kernel matrix: right-preconditioned restarted GMRES on the device ---------------------
+const Kernel<double>::Model& Kernel<double>::krylov_model(const char* what, double rtol, int maxit, int restart) const {
+  const Model& M = model(what);
+  if (device_type() != 0 && device_type() != 1) throw std::invalid_argument(std::string(what) + ": Gauss and Laplace kernels only (no ANOVA product)");
+  if (!(rtol > 0.) || !std::isfinite(rtol)) throw std::invalid_argument(std::string(what) + ": rtol must be positive and finite");
+  if (maxit < 1 || restart < 1) throw std::invalid_argument(std::string(what) + ": maxit and restart must be at least 1");
+  // Stopwatches 4 / 5 / 6 are not this code's alone (the compression and the prediction statistics use them too): whatever an
+  // earlier caller that threw between its start and its read left recorded there is dropped, so that this call reads its own pairs.
+  for (int w = 4; w <= 6; w++) hssk_watch_read_ms(M.ctx(), w, nullptr);
+  kry_ms_[0] = kry_ms_[1] = kry_ms_[2] = 0.;
+  return M;
+}
+
+void Kernel<double>::krylov_finish(const Model& M, KrylovInfo& info) const {
+  for (int w = 0; w < 3; w++) info.ms[w] = kry_ms_[w] = hssk_watch_read_ms(M.ctx(), w + 4, nullptr);
+}
+
+// Stopwatches 4 / 5 / 6: products, solves, Krylov kernels (1 .. 3 belong to the variance loop this may run inside).
+void Kernel<double>::krylov_block(const Model& M, KrylovWork& ws, int nc, double* dX, const double* dB, double rtol, int maxit, int restart,
+                                  KrylovInfo& info) const {
+  hssk_ctx* ctx = M.ctx();
+  const long long nn = (long long)n();
+  const int m = ws.m, ldh = m + 2;
+  const size_t blk = (size_t)nn * nc;
+  const hssk_kernel_spec spec{M.dX, nn, int(d()), device_type(), degree(), width(), lambda_};
+  // ||b|| per column
+  std::vector<double> bn(nc, 0.), nrm(nc, 0.), res0(nc, 0.), res(nc, 0.);
+  hssk_watch_start(ctx, 6);
+  ckk(hssk_coldots(ctx, dB, nn, dB, nn, nn, nc, ws.norms));
+  hssk_watch_stop(ctx, 6);
+  ckk(hssk_memcpy_d2h(ctx, bn.data(), ws.norms, (long long)sizeof(double) * nc));
+  for (int c = 0; c < nc; c++) {
+    bn[c] = std::sqrt(bn[c]);
+    if (!(bn[c] > 0.)) ckk(hssk_memset_zero(ctx, dX + (size_t)c * nn, (long long)sizeof(double) * nn));   // b = 0: x = 0
+  }
+  // per column: R (m x m, upper triangle of the rotated Hessenberg matrix), the rotations, the rotated right-hand side
+  std::vector<double> R((size_t)nc * m * m), cs((size_t)nc * m), sn((size_t)nc * m), g((size_t)nc * (m + 1)), Y((size_t)nc * m),
+      H((size_t)nc * ldh);
+  std::vector<int> its(nc, 0), kc(nc, 0);
+  std::vector<char> conv(nc, 0);
+  int steps = 0;
+  bool first = true, all = false;
+  for (;;) {
+    // 1. the true residual of every column
+    hssk_watch_start(ctx, 4);
+    ckk(hssk_kernel_matmul(ctx, &spec, 0, dX, nn, nc, ws.W, nn, 0));
+    hssk_watch_stop(ctx, 4);
+    info.products++;
+    hssk_watch_start(ctx, 6);
+    ckk(hssk_krylov_start(ctx, dB, nn, ws.W, nn, nn, nc, ws.V, nn, ws.norms));
+    hssk_watch_stop(ctx, 6);
+    ckk(hssk_memcpy_d2h(ctx, nrm.data(), ws.norms, (long long)sizeof(double) * nc));
+    // 2. who is done
+    unsigned long long active = 0;
+    for (int c = 0; c < nc; c++) {
+      res[c] = bn[c] > 0. ? nrm[c] / bn[c] : 0.;
+      conv[c] = !(bn[c] > 0.) || nrm[c] <= rtol * bn[c];
+      if (!conv[c]) active |= 1ULL << c;
+    }
+    if (first) { res0 = res; first = false; }
+    all = active == 0;
+    if (all || steps >= maxit) break;
+    info.cycles++;
+    for (int c = 0; c < nc; c++) { kc[c] = 0; g[(size_t)c * (m + 1)] = nrm[c]; }
+    // 3. the steps of the cycle
+    for (int k = 0; k < m; k++) {
+      ckk(hssk_memcpy_d2d(ctx, ws.Z, ws.V + (size_t)k * blk, (long long)sizeof(double) * blk));
+      hssk_watch_start(ctx, 5);
+      M.H.solve_device(nc, ws.Z, nn);
+      hssk_watch_stop(ctx, 5);
+      info.solves++;
+      hssk_watch_start(ctx, 4);
+      ckk(hssk_kernel_matmul(ctx, &spec, 0, ws.Z, nn, nc, ws.W, nn, 0));
+      hssk_watch_stop(ctx, 4);
+      info.products++;
+      hssk_watch_start(ctx, 6);
+      ckk(hssk_krylov_orth(ctx, ws.V, nn, nn, nc, k, ws.W, nn, active, ws.Hout, ldh));
+      hssk_watch_stop(ctx, 6);
+      ckk(hssk_memcpy_d2h(ctx, H.data(), ws.Hout, (long long)sizeof(double) * ldh * nc));   // (the only read-back of a step)
+      steps++;
+      for (int c = 0; c < nc; c++) {
+        if (!((active >> c) & 1ULL)) continue;
+        its[c]++;
+        double* h = H.data() + (size_t)c * ldh;
+        double *Rc = R.data() + (size_t)c * m * m, *cc = cs.data() + (size_t)c * m, *sc = sn.data() + (size_t)c * m, *gc = g.data() + (size_t)c * (m + 1);
+        const double below = h[k + 1];
+        for (int i = 0; i < k; i++) {
+          const double t = cc[i] * h[i] + sc[i] * h[i + 1];
+          h[i + 1] = -sc[i] * h[i] + cc[i] * h[i + 1];
+          h[i] = t;
+        }
+        const double r = std::hypot(h[k], h[k + 1]);
+        if (!(r > 0.) || !std::isfinite(r)) {   // a column of zeros (or not a number): the step adds nothing, the column rests
+          active &= ~(1ULL << c);
+          continue;
+        }
+        cc[k] = h[k] / r;
+        sc[k] = h[k + 1] / r;
+        h[k] = r;
+        for (int i = 0; i <= k; i++) Rc[i + (size_t)k * m] = h[i];
+        gc[k + 1] = -sc[k] * gc[k];
+        gc[k] = cc[k] * gc[k];
+        kc[c] = k + 1;
+        if (std::abs(gc[k + 1]) <= rtol * bn[c] || below == 0.) active &= ~(1ULL << c);
+      }
+      if (!active || steps >= maxit) break;
+    }
+    // 4. x += M^-1 (V y), every column with its own number of steps
+    int kmax = 0;
+    std::fill(Y.begin(), Y.end(), 0.);
+    for (int c = 0; c < nc; c++) {
+      const double *Rc = R.data() + (size_t)c * m * m, *gc = g.data() + (size_t)c * (m + 1);
+      double* y = Y.data() + (size_t)c * m;
+      for (int i = kc[c] - 1; i >= 0; i--) {
+        double s = gc[i];
+        for (int j = i + 1; j < kc[c]; j++) s -= Rc[i + (size_t)j * m] * y[j];
+        y[i] = s / Rc[i + (size_t)i * m];
+      }
+      kmax = std::max(kmax, kc[c]);
+    }
+    if (kmax == 0) break;   // (no column moved: nothing more to gain)
+    ckk(hssk_memcpy_h2d(ctx, ws.Y, Y.data(), (long long)sizeof(double) * m * nc));
+    hssk_watch_start(ctx, 6);
+    ckk(hssk_krylov_combine(ctx, ws.V, nn, nn, nc, kmax, ws.Y, m, ws.U, nn, 0));
+    hssk_watch_stop(ctx, 6);
+    hssk_watch_start(ctx, 5);
+    M.H.solve_device(nc, ws.U, nn);
+    hssk_watch_stop(ctx, 5);
+    info.solves++;
+    hssk_watch_start(ctx, 6);
+    ckk(hssk_krylov_combine(ctx, ws.U, nn, nn, nc, 1, ws.ones, 1, dX, nn, 1));
+    hssk_watch_stop(ctx, 6);
+  }
+  for (int c = 0; c < nc; c++) {
+    info.converged = info.converged && conv[c];
+    info.iterations = std::max(info.iterations, its[c]);
+    info.its.push_back(its[c]);
+    info.residual.push_back(res[c]);
+    info.residual0.push_back(res0[c]);
+  }
+}
+
+KrylovInfo Kernel<double>::model_refine(double rtol, int maxit, int restart) {
+  const Model& M = krylov_model("model_refine", rtol, maxit, restart);
+  hssk_ctx* ctx = M.ctx();
+  const long long nn = (long long)n();
+  KrylovInfo info;
+  KrylovWork ws(ctx, nn, 1, maxit, restart, true);
+  ckk(hssk_memcpy_h2d(ctx, ws.B, M.labels.data(), (long long)sizeof(double) * nn));
+  ckk(hssk_memcpy_h2d(ctx, ws.X, M.weights.data(), (long long)sizeof(double) * nn));
+  krylov_block(M, ws, 1, ws.X, ws.B, rtol, maxit, restart, info);
+  DenseMatrix<double> w(n(), 1);
+  ckk(hssk_memcpy_d2h(ctx, w.data(), ws.X, (long long)sizeof(double) * nn));
+  krylov_finish(M, info);
+  model_->weights = w;
+  return info;
+}
+
+DenseMatrix<double> Kernel<double>::model_solve(const DenseMatrix<double>& B, KrylovInfo* info, double rtol, int maxit, int restart) const {
+  const Model& M = krylov_model("model_solve", rtol, maxit, restart);
+  if (B.rows() != n()) throw std::invalid_argument("model_solve: one row per training point expected (cluster order)");
+  hssk_ctx* ctx = M.ctx();
+  const long long nn = (long long)n();
+  const int m = int(B.cols()), CH = 64;
+  KrylovInfo local;
+  DenseMatrix<double> X(n(), m);
+  if (m > 0) {
+    KrylovWork ws(ctx, nn, std::min(m, CH), maxit, restart, true);
+    for (int c0 = 0; c0 < m; c0 += CH) {
+      const int nc = std::min(CH, m - c0);
+      ckk(hssk_memcpy2d_h2d(ctx, ws.B, sizeof(double) * nn, B.ptr(0, c0), sizeof(double) * B.ld(), sizeof(double) * nn, nc));
+      ckk(hssk_memcpy_d2d(ctx, ws.X, ws.B, (long long)sizeof(double) * nn * nc));
+      hssk_watch_start(ctx, 5);
+      M.H.solve_device(nc, ws.X, nn);   // the first iterate H^-1 b
+      hssk_watch_stop(ctx, 5);
+      local.solves++;
+      krylov_block(M, ws, nc, ws.X, ws.B, rtol, maxit, restart, local);
+      ckk(hssk_memcpy2d_d2h(ctx, X.ptr(0, c0), sizeof(double) * X.ld(), ws.X, sizeof(double) * nn, sizeof(double) * nn, nc));
+    }
+    krylov_finish(M, local);
+  }
+  if (info) *info = local;
+  return X;
 }
 
 DenseMatrix<double> Kernel<double>::fit_HSS(std::vector<double>& labels, const HSS::HSSOptions<double>& opts) {
@@ -798,6 +1024,62 @@ int SPX_kernel_gradient_ms(STRUMPACKKernel K, double* out) {
   auto k = model_of(K);
   if (!k || !out) return 1;
   std::copy(k->gradient_ms(), k->gradient_ms() + 3, out);
+  return 0;
+}
+
+// ---- solves with the exact kernel matrix ----
+namespace {
+// info: 8 + 2 m doubles (include/kernel/Kernel.h)
+void krylov_info_out(const kernel::KrylovInfo& I, double* info) {
+  if (!info) return;
+  const std::size_t m = I.its.size();
+  info[0] = I.converged ? 1. : 0.; info[1] = I.iterations; info[2] = (double)I.products; info[3] = (double)I.solves; info[4] = (double)I.cycles;
+  info[5] = m ? *std::max_element(I.residual0.begin(), I.residual0.end()) : 0.;
+  info[6] = m ? *std::max_element(I.residual.begin(), I.residual.end()) : 0.;
+  info[7] = (double)m;
+  std::copy(I.residual.begin(), I.residual.end(), info + 8);
+  for (std::size_t c = 0; c < m; c++) info[8 + m + c] = I.its[c];
+}
+}  // namespace
+int SPX_kernel_model_refine(STRUMPACKKernel K, double rtol, int maxit, int restart, double* info) {
+  try {
+    auto k = model_of(K);
+    if (!k) return 1;
+    const kernel::KrylovInfo I = k->model_refine(rtol, maxit, restart);
+    static_cast<KernelRegression*>(K)->weights = k->model_weights();
+    krylov_info_out(I, info);
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_model_solve(STRUMPACKKernel K, int m, const double* B, int ldb, double* X, int ldx, double rtol, int maxit, int restart,
+                           double* info) {
+  try {
+    auto k = model_of(K);
+    if (!k || m < 0 || (m > 0 && (!B || !X || ldb < (int)k->n() || ldx < (int)k->n()))) return 1;
+    kernel::KrylovInfo I;
+    const DenseMatrix<double> S = k->model_solve(DenseMatrix<double>(k->n(), m, B, ldb), &I, rtol, maxit, restart);
+    for (int c = 0; c < m; c++) std::copy(S.ptr(0, c), S.ptr(0, c) + k->n(), X + (size_t)c * ldx);
+    krylov_info_out(I, info);
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_predict_variance_exact_double(STRUMPACKKernel K, int m, const double* test, double* var, double rtol, int maxit, int restart,
+                                             double* info) {
+  try {
+    auto k = model_of(K);
+    if (!k || m < 0 || (m > 0 && (!test || !var))) return 1;
+    kernel::KrylovInfo I;
+    DenseMatrix<double> t(k->d(), m, test, k->d());
+    const std::vector<double> v = k->predict_variance_exact(t, &I, rtol, maxit, restart);
+    std::copy(v.begin(), v.end(), var);
+    krylov_info_out(I, info);
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_krylov_ms(STRUMPACKKernel K, double out[3]) {
+  auto k = model_of(K);
+  if (!k || !out || (k->device_type() != 0 && k->device_type() != 1)) return 1;   // (ANOVA: none of the three calls exists)
+  std::copy(k->krylov_ms(), k->krylov_ms() + 3, out);
   return 0;
 }
 

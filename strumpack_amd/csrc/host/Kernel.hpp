@@ -51,6 +51,16 @@ struct LmlGradient {
   std::vector<double> th, tl;                 // per probe: s_k^T (dK/dh z_k), s_k^T z_k
 };
 
+// what the solves with the EXACT kernel matrix report (Kernel<double>::model_refine / model_solve / predict_variance_exact)
+struct KrylovInfo {
+  bool converged = true;                        // every column reached rtol
+  int iterations = 0;                           // steps of the slowest column
+  long long products = 0, solves = 0, cycles = 0;   // exact products, ULV solves and restart cycles, summed over the blocks
+  std::vector<int> its;                         // per column: steps it took part in
+  std::vector<double> residual, residual0;      // per column: ||b - (K + lambda I) x|| / ||b|| at the end and at the start (true ones)
+  double ms[3] = {0., 0., 0.};                  // device-clock milliseconds: products, solves, Krylov kernels
+};
+
 template <> class Kernel<double> {
   using scalar_t = double;
   using DenseM_t = DenseMatrix<double>;
@@ -118,6 +128,27 @@ template <> class Kernel<double> {
   scalar_t model_residual() const;
   // device-clock milliseconds of the last gradient call: kernel products, solves, column dot products (profiling)
   const double* gradient_ms() const { return grad_ms_; }
+  // ---- extension: solves with the EXACT K + lambda I, the kept ULV factors as preconditioner (Gauss and Laplace).
+  // Right-preconditioned restarted GMRES, device resident, up to 64 columns in lockstep: per step one ULV solve, one exact product
+  // (hssk_kernel_matmul) and one orthogonalisation (hssk_krylov_orth), the small least-squares problems per column on the host.
+  // A column is converged when its TRUE residual, computed at the start of a cycle, is at most rtol ||b||; the total number of
+  // steps never exceeds maxit (not converging is reported, not thrown); restart + 6 blocks of n x 64 doubles come from the
+  // device pool for the length of the call.  Throws for rtol <= 0 or not finite, maxit < 1, restart < 1, an ANOVA kernel.
+  //
+  // model_refine: the kept labels as right-hand side, the current weights as first iterate; the model's weights become the last
+  // iterate (GMRES residuals do not increase), so model_weights(), model_residual() and the y^T alpha of
+  // log_marginal_likelihood() follow.  logabsdet() -- and with it the second term of the likelihood -- stays that of the
+  // COMPRESSED matrix.  model_set_lambda and a new fit replace the weights by the compressed solve again.
+  KrylovInfo model_refine(scalar_t rtol = 1e-8, int maxit = 100, int restart = 30);
+  // X = (K + lambda I)^-1 B for any number of columns (rows in cluster order), in blocks of 64, from the first iterate H^-1 b; the
+  // model is not changed.  info (may be null): the per-column data concatenated, the counts summed.
+  DenseM_t model_solve(const DenseM_t& B, KrylovInfo* info = nullptr, scalar_t rtol = 1e-8, int maxit = 100, int restart = 30) const;
+  // predict_variance with the exact solve in place of the compressed one: var[c] = k(t_c, t_c) - k_c^T (K + lambda I)^-1 k_c up
+  // to rtol.  Not clamped.
+  std::vector<scalar_t> predict_variance_exact(const DenseM_t& test, KrylovInfo* info = nullptr, scalar_t rtol = 1e-8, int maxit = 100,
+                                               int restart = 30) const;
+  // device-clock milliseconds of the last of these three calls: exact products, ULV solves, Krylov kernels (profiling)
+  const double* krylov_ms() const { return kry_ms_; }
 
   const DenseM_t& data() const { return data_; }
   DenseM_t& data() { return data_; }
@@ -150,7 +181,17 @@ template <> class Kernel<double> {
   bool keep_model_ = false;
   mutable double var_ms_[3] = {0., 0., 0.};
   mutable double grad_ms_[3] = {0., 0., 0.};
+  mutable double kry_ms_[3] = {0., 0., 0.};
   const Model& model(const char* what) const;
+  struct KrylovWork;   // the device blocks of a Krylov call (Kernel.cpp)
+  const Model& krylov_model(const char* what, scalar_t rtol, int maxit, int restart) const;
+  // one block of at most 64 columns: dX (first iterate in, last iterate out) and dB are n x nc device blocks, leading dimension n
+  void krylov_block(const Model& M, KrylovWork& ws, int nc, double* dX, const double* dB, scalar_t rtol, int maxit, int restart,
+                    KrylovInfo& info) const;
+  void krylov_finish(const Model& M, KrylovInfo& info) const;
+  // the chunk loop of both variance calls; ws == nullptr: the compressed solve
+  std::vector<scalar_t> variance_chunks(const Model& M, const DenseM_t& test, KrylovWork* ws, scalar_t rtol, int maxit, int restart,
+                                        KrylovInfo* info) const;
 };
 
 template <typename scalar_t> class GaussKernel;

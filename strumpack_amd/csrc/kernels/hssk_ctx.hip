@@ -293,6 +293,7 @@ void hssk_ctx_destroy(hssk_ctx* c) {
   hssk_rt::dev_free(c->d_aux);
   hssk_rt::dev_free(c->d_gen);
   hssk_rt::dev_free(c->d_kmm);
+  hssk_rt::dev_free(c->d_kry);
   delete c->uploader;
   hssk_rt::pinned_free(c->h_sweep_err);
   for (auto& w : c->watch) for (auto& p : w) { hssk_rt::event_destroy(p.first); hssk_rt::event_destroy(p.second); }

@@ -158,6 +158,19 @@ struct hssk_ctx {
     }
     return d_kmm;
   }
+  // coefficients and chunk partials of the Krylov kernels (hssk_krylov.hip): a buffer of its own for the same reason
+  double* d_kry = nullptr;
+  size_t kry_bytes = 0;
+  double* kry_work(size_t bytes) {
+    if (bytes > kry_bytes) {
+      sync_all();
+      hssk_rt::dev_free(d_kry);
+      d_kry = nullptr; kry_bytes = 0;
+      d_kry = (double*)hssk_rt::dev_malloc(bytes);
+      kry_bytes = bytes;
+    }
+    return d_kry;
+  }
   double* scratch(size_t bytes) {
     if (bytes > scratch_bytes) {
       sync_all();

@@ -172,6 +172,7 @@ HSSK_SYMBOLS = [
     "hssk_kernel_predict_f32", "hssk_kernel_predict_f32_wide", "hssk_kernel_predict_splits",
     "hssk_logabsdet_vbatched", "hssk_kernel_cross", "hssk_kernel_predict_cols",
     "hssk_kernel_matmul", "hssk_kernel_matmul_splits", "hssk_coldots",
+    "hssk_krylov_start", "hssk_krylov_orth", "hssk_krylov_combine",
 ]
 
 
@@ -298,6 +299,12 @@ class Hssk:
                                          C.c_int]
         L.hssk_kernel_matmul_splits.argtypes = [C.c_longlong]
         L.hssk_coldots.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p]
+        L.hssk_krylov_start.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int,
+                                        C.c_void_p, C.c_longlong, C.c_void_p]
+        L.hssk_krylov_orth.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_longlong,
+                                       C.c_ulonglong, C.c_void_p, C.c_longlong]
+        L.hssk_krylov_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_longlong, C.c_void_p, C.c_longlong, C.c_int]
         L.hssk_colsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.hssk_cluster_median.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         for fn in ("hssk_pchol_id_vbatched", "hssk_sum_partials", "hssk_gram_vbatched"):

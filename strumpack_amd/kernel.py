@@ -14,7 +14,8 @@ KERNEL_SYMBOLS = [
     "SPX_kernel_keep_model", "SPX_kernel_logabsdet", "SPX_kernel_log_marginal_likelihood", "SPX_kernel_predict_variance_double",
     "SPX_kernel_variance_ms", "SPX_kernel_model_set_lambda", "SPX_kernel_model_write", "SPX_kernel_model_labels",
     "SPX_kernel_model_points", "SPX_kernel_lml_gradient", "SPX_kernel_model_probes", "SPX_kernel_model_residual",
-    "SPX_kernel_gradient_ms",
+    "SPX_kernel_gradient_ms", "SPX_kernel_model_refine", "SPX_kernel_model_solve", "SPX_kernel_predict_variance_exact_double",
+    "SPX_kernel_krylov_ms",
 ]
 KERNEL_TYPES = {"Gauss": 0, "rbf": 0, "Laplace": 1, "ANOVA": 2}
 CLUSTERING = {"natural": 0, "2means": 1, "kdtree": 2, "pca": 3, "cobble": 4}
@@ -55,6 +56,10 @@ def load(path):
     L.SPX_kernel_model_probes.argtypes = [vp, C.c_int, C.c_ulonglong, vp]
     L.SPX_kernel_model_residual.argtypes = [vp, C.POINTER(C.c_double)]
     L.SPX_kernel_gradient_ms.argtypes = [vp, vp]
+    L.SPX_kernel_model_refine.argtypes = [vp, C.c_double, C.c_int, C.c_int, vp]
+    L.SPX_kernel_model_solve.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp]
+    L.SPX_kernel_predict_variance_exact_double.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, vp]
+    L.SPX_kernel_krylov_ms.argtypes = [vp, vp]
     L.SPX_clustering.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int]
     L.SPX_clustering_device.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
     return L
@@ -106,14 +111,66 @@ class KernelRegression:
             raise RuntimeError("SPX_kernel_log_marginal_likelihood failed (no kept model)")
         return out.value
 
-    def predict_variance(self, T):
+    def predict_variance(self, T, exact=False, rtol=1e-8, maxit=100, restart=30, info=False):
         """variance of the latent function at the rows of T (add lam for the observation noise); not clamped: the compressed
-        matrix is K + lam I only up to the compression tolerance, so a value may be slightly negative"""
+        matrix is K + lam I only up to the compression tolerance, so a value may be slightly negative.  exact=True: the solve
+        with the exact kernel matrix instead (see refine), up to rtol; info=True then also returns the dict of that solve"""
         T = np.ascontiguousarray(T, dtype=np.float64)
         out = np.zeros(T.shape[0])
-        if self.L.SPX_kernel_predict_variance_double(self.K, T.shape[0], T.ctypes.data, out.ctypes.data):
-            raise RuntimeError("SPX_kernel_predict_variance_double failed (no kept model)")
-        return out
+        if not exact:
+            if self.L.SPX_kernel_predict_variance_double(self.K, T.shape[0], T.ctypes.data, out.ctypes.data):
+                raise RuntimeError("SPX_kernel_predict_variance_double failed (no kept model)")
+            return out
+        buf = np.zeros(8 + 2 * T.shape[0])
+        if self.L.SPX_kernel_predict_variance_exact_double(self.K, T.shape[0], T.ctypes.data, out.ctypes.data, float(rtol), int(maxit),
+                                                           int(restart), buf.ctypes.data):
+            raise RuntimeError("SPX_kernel_predict_variance_exact_double failed (a kept model of a Gauss or Laplace fit and valid "
+                               "rtol / maxit / restart are needed)")
+        return (out, self._krylov_info(buf)) if info else out
+
+    @staticmethod
+    def _krylov_info(buf):
+        m = int(buf[7])
+        return dict(converged=bool(buf[0]), iterations=int(buf[1]), products=int(buf[2]), solves=int(buf[3]), cycles=int(buf[4]),
+                    residual0=float(buf[5]), residual_max=float(buf[6]), residual=buf[8:8 + m].copy(),
+                    its=buf[8 + m:8 + 2 * m].astype(np.int64))
+
+    def refine(self, rtol=1e-8, maxit=100, restart=30):
+        """weights of the EXACT K + lam I: restarted GMRES on the device with the kept factors as preconditioner, from the
+        current weights.  weights(), decision_function, fit_residual and log_marginal_likelihood follow; logabsdet stays that of
+        the compressed matrix.  Returns a dict: converged, iterations, products, solves, cycles, residual0 (before), residual
+        (after; both true relative residuals), its.  Not converging within maxit steps is reported, not raised."""
+        buf = np.zeros(10)
+        if self.L.SPX_kernel_model_refine(self.K, float(rtol), int(maxit), int(restart), buf.ctypes.data):
+            raise RuntimeError("SPX_kernel_model_refine failed (a kept model of a Gauss or Laplace fit and valid rtol / maxit / restart "
+                               "are needed)")
+        d = self._krylov_info(buf)
+        d["residual"] = float(d["residual"][0])
+        d["its"] = int(d["its"][0])
+        del d["residual_max"]
+        return d
+
+    def solve(self, B, rtol=1e-8, maxit=100, restart=30):
+        """(X, dict) with (K + lam I) X = B for the exact kernel matrix; B: n or n x m, rows in cluster order (the order of
+        model_points()).  The model is not changed.  residual and its of the dict are per column."""
+        B = np.asarray(B, dtype=np.float64)
+        one = B.ndim == 1
+        B = np.asfortranarray(B.reshape(len(B), -1))
+        if B.shape[0] != self.n:
+            raise ValueError("solve: B must have n rows")
+        m = B.shape[1]
+        X, buf = np.zeros((self.n, m), order="F"), np.zeros(8 + 2 * m)
+        if self.L.SPX_kernel_model_solve(self.K, m, B.ctypes.data, self.n, X.ctypes.data, self.n, float(rtol), int(maxit), int(restart),
+                                         buf.ctypes.data):
+            raise RuntimeError("SPX_kernel_model_solve failed (a kept model of a Gauss or Laplace fit and valid rtol / maxit / restart "
+                               "are needed)")
+        return (X[:, 0] if one else X), self._krylov_info(buf)
+
+    def krylov_ms(self):
+        out = np.zeros(3)
+        if self.L.SPX_kernel_krylov_ms(self.K, out.ctypes.data):
+            raise RuntimeError("no kept double-precision Gauss or Laplace model")
+        return dict(zip(["product_ms", "solve_ms", "krylov_ms"], out.tolist()))
 
     def variance_ms(self):
         out = np.zeros(3)
