@@ -861,6 +861,31 @@ int hssk_logabsdet_vbatched(hssk_ctx* ctx, const hssk_logdet_desc* descs, int co
 int hssk_kernel_matmul(hssk_ctx* ctx, const hssk_kernel_spec* spec, int deriv, const double* B, long long ldb, int nc, double* out,
                        long long ldo, int splits);
 int hssk_kernel_matmul_splits(long long n);   /* what splits = 0 chooses: a function of n alone */
+/* ---- the same product in single precision per pair: the inner operator of the mixed-precision solves ----------
+ * The promise of hssk_kernel_matmul_f32's matrix-core route: the worst error the norm expansion |x|^2 + |y|^2 - 2 x.y can add to
+ * a base-2 exponent, 4 (d + 4) 2^-24 (max |x~|^2 of the row tile + max |x~|^2 of the training tile).  A pair of tiles above it is
+ * computed from FP32 differences instead.  Much tighter than HSSK_KPREDICT_TAU: an operator error of 1e-4 costs GMRES ten times
+ * the steps; 2^-17 is the difference form's own error at an exponent of 16 in R^8. */
+#define HSSK_KMATMUL_F32_TAU 7.62939453125e-6 /* 2^-17 */
+/* bytes of the prepared points of hssk_kernel_matmul_f32 for n points in R^d (1 <= d <= 64; -1 otherwise) */
+long long hssk_kernel_matmul_f32_prep_bytes(long long n, int d);
+/* The points of spec (FP64, device) centred in FP64 (the mean in a fixed order), scaled, rounded once to float and laid out for
+ * hssk_kernel_matmul_f32 in `prep` (device, at least hssk_kernel_matmul_f32_prep_bytes): once per point set and width, not per
+ * product.  Gauss and Laplace, d <= 64; anything else returns HSSK_UNSUPPORTED (2) and writes nothing. */
+int hssk_kernel_matmul_f32_prep(hssk_ctx* ctx, const hssk_kernel_spec* spec, void* prep, long long bytes);
+/* out(i, c) = sum_r k32(x_i, x_r) B(r, c) + spec->lambda B(i, c), 1 <= nc <= 64: B and out are FP64 blocks as for
+ * hssk_kernel_matmul (column-major, ldb, ldo >= n, no aliasing, rows n .. ld - 1 never touched); B is rounded to float as it is
+ * staged.  k32: FP32 from the prepared points -- Gauss tiles under HSSK_KMATMUL_F32_TAU on the matrix cores (norm expansion over
+ * K = d + 2, exp2), every other tile in the FP32 difference form; the pair r == i is exactly 1.  g times B on the FP32 matrix
+ * cores, no FP32 sum longer than 64 training points, FP64 across chunks and splits; lambda B(i, c) in FP64 from the unrounded B.
+ * Grid and splits as for hssk_kernel_matmul (splits = 0: hssk_kernel_matmul_f32_splits(n); at most one split per 64 training
+ * points).  No atomics on results: bitwise repeatable, and a column does not depend on the other columns.  ANOVA and d > 64 return
+ * HSSK_UNSUPPORTED (2), nc outside 1 .. 64, bad leading dimensions and null pointers 1, stage buffers above the device's LDS 2;
+ * the outputs are then untouched.  stats (host, 4 values, may be NULL; the call synchronises when given): [0] pairs of tiles
+ * (64 rows x 64 training points) on the matrix-core route, [1] in the difference form, [2] splits, [3] device-clock microseconds. */
+int hssk_kernel_matmul_f32(hssk_ctx* ctx, const hssk_kernel_spec* spec, const void* prep, const double* B, long long ldb, int nc,
+                           double* out, long long ldo, int splits, long long* stats);
+int hssk_kernel_matmul_f32_splits(long long n);   /* what splits = 0 chooses: a function of n alone */
 /* out[c] = sum_{i < n} A(i, c) B(i, c), c < nc (A, B: device, column-major, lda, ldb >= n; out: device, nc doubles).  One
  * workgroup per column, fixed summation order, no atomics: bitwise repeatable. */
 int hssk_coldots(hssk_ctx* ctx, const double* A, long long lda, const double* B, long long ldb, long long n, int nc, double* out);

@@ -117,6 +117,20 @@ int SPX_kernel_predict_variance_exact_double(STRUMPACKKernel K, int m, const dou
 /* device-clock milliseconds of the last of these three calls: out[0] exact products, [1] ULV solves, [2] Krylov kernels (zeros
  * before the first one).  Refused like them: no kept model, a float handle, a user-defined or ANOVA kernel. */
 int SPX_kernel_krylov_ms(STRUMPACKKernel K, double out[3]);
+/* ---- mixed precision for the three calls above.  Handle state of a double handle with a built-in kernel, set like
+ * SPX_kernel_keep_model (before or after the fit; a new lambda leaves it alone).  precision 0: FP64 (the default: every call is
+ * what it was, bit for bit); 1: the product inside the restart cycles is the FP32 matrix-core product hssk_kernel_matmul_f32,
+ * the true residual at every cycle's start -- where convergence is declared -- stays FP64.  inner_rtol: a column leaves its
+ * cycle when the Arnoldi estimate is at most max(rtol ||b||, inner_rtol ||r at the cycle's start||); <= 0 takes the default
+ * (1e-4), otherwise it must be below 1.  Non-zero and nothing changed: a float handle, an unknown precision, inner_rtol >= 1 or
+ * not a number.  With precision 1 the three calls are also refused (model untouched) for more than 64 coordinates; ANOVA is
+ * refused as before.  If a true residual does not decrease from one cycle start to the next, the rest of that block of columns
+ * runs with the FP64 product: counted in the statistics, not an error. */
+int SPX_kernel_set_krylov_inner(STRUMPACKKernel K, int precision, double inner_rtol);
+int SPX_kernel_krylov_inner(STRUMPACKKernel K, int* precision, double* inner_rtol);
+/* of the last of the three calls: out[0] FP64 products, [1] FP32 products, [2] fallbacks, [3] cycles, [4] ms of the FP64 products,
+ * [5] ms of the FP32 products.  Refused like SPX_kernel_krylov_ms. */
+int SPX_kernel_krylov_stats(STRUMPACKKernel K, double out[6]);
 /* binary_tree_clustering on its own (clustering/Clustering.hpp:143-168): algo 0 natural, 1 2means, 2 kdtree,
  * 3 pca, 4 cobble; data (d x n) is reordered in place, perm is 1-based; returns the number of leaves and writes
  * at most cap leaf sizes */

@@ -93,12 +93,16 @@ struct GradBuf {   // a device pool chunk for the length of a call
 struct Kernel<double>::KrylovWork {
   long long n;
   int ncmax, m;   // m: steps of a cycle = min(restart, maxit)
-  GradBuf bV, bZ, bW, bU, bB, bX, bS;
+  GradBuf bV, bZ, bW, bU, bB, bX, bS, bP;
   double *V, *Z, *W, *U, *B, *X, *Y, *Hout, *norms, *ones;
-  KrylovWork(hssk_ctx* ctx, long long n_, int ncmax_, int maxit, int restart, bool own_bx)
+  void* prep = nullptr;   // mixed mode: the prepared float points of hssk_kernel_matmul_f32 (prep_bytes > 0)
+  std::size_t prep_bytes;
+  KrylovWork(hssk_ctx* ctx, long long n_, int ncmax_, int maxit, int restart, bool own_bx, std::size_t prep_bytes_ = 0)
       : n(n_), ncmax(ncmax_), m(std::min(restart, maxit)), bV(ctx, sizeof(double) * n_ * ncmax_ * (size_t)(m + 1)), bZ(ctx, sizeof(double) * n_ * ncmax_),
         bW(ctx, sizeof(double) * n_ * ncmax_), bU(ctx, sizeof(double) * n_ * ncmax_), bB(ctx, sizeof(double) * n_ * ncmax_),
-        bX(ctx, own_bx ? sizeof(double) * n_ * ncmax_ : 0), bS(ctx, sizeof(double) * (size_t)ncmax_ * (2 * m + 4)) {
+        bX(ctx, own_bx ? sizeof(double) * n_ * ncmax_ : 0), bS(ctx, sizeof(double) * (size_t)ncmax_ * (2 * m + 4)), bP(ctx, prep_bytes_),
+        prep_bytes(prep_bytes_) {
+    if (prep_bytes) prep = bP.p;
     V = (double*)bV.p; Z = (double*)bZ.p; W = (double*)bW.p; U = (double*)bU.p; B = (double*)bB.p; X = (double*)bX.p;
     Y = (double*)bS.p; Hout = Y + (size_t)ncmax * m; norms = Hout + (size_t)ncmax * (m + 2); ones = norms + ncmax;
     const std::vector<double> one(ncmax, 1.);
@@ -117,7 +121,8 @@ std::vector<double> Kernel<double>::predict_variance_exact(const DenseMatrix<dou
   if (test.rows() != d()) throw std::invalid_argument("predict_variance_exact: test points have the wrong dimension");
   KrylovInfo local;
   if (test.cols() == 0) { if (info) *info = local; return {}; }
-  KrylovWork ws(M.ctx(), (long long)n(), 64, maxit, restart, false);
+  KrylovWork ws(M.ctx(), (long long)n(), 64, maxit, restart, false, krylov_prep_bytes());
+  krylov_prepare(M, ws);
   std::vector<double> var = variance_chunks(M, test, &ws, rtol, maxit, restart, &local);
   krylov_finish(M, local);
   if (info) *info = local;
@@ -269,15 +274,41 @@ const Kernel<double>::Model& Kernel<double>::krylov_model(const char* what, doub
   if (device_type() != 0 && device_type() != 1) throw std::invalid_argument(std::string(what) + ": Gauss and Laplace kernels only (no ANOVA product)");
   if (!(rtol > 0.) || !std::isfinite(rtol)) throw std::invalid_argument(std::string(what) + ": rtol must be positive and finite");
   if (maxit < 1 || restart < 1) throw std::invalid_argument(std::string(what) + ": maxit and restart must be at least 1");
+  if (inner_ == KrylovInner::FP32 && d() > 64)
+    throw std::invalid_argument(std::string(what) + ": the FP32 inner product takes at most 64 coordinates (krylov_inner)");
   // Stopwatches 4 / 5 / 6 are not this code's alone (the compression and the prediction statistics use them too): whatever an
   // earlier caller that threw between its start and its read left recorded there is dropped, so that this call reads its own pairs.
   for (int w = 4; w <= 6; w++) hssk_watch_read_ms(M.ctx(), w, nullptr);
-  kry_ms_[0] = kry_ms_[1] = kry_ms_[2] = 0.;
+  if (inner_ == KrylovInner::FP32) hssk_watch_read_ms(M.ctx(), 7, nullptr);
+  kry_ms_[0] = kry_ms_[1] = kry_ms_[2] = kry_ms_[3] = 0.;
   return M;
 }
 
 void Kernel<double>::krylov_finish(const Model& M, KrylovInfo& info) const {
   for (int w = 0; w < 3; w++) info.ms[w] = kry_ms_[w] = hssk_watch_read_ms(M.ctx(), w + 4, nullptr);
+  info.ms[3] = kry_ms_[3] = inner_ == KrylovInner::FP32 ? hssk_watch_read_ms(M.ctx(), 7, nullptr) : 0.;
+  const double st[6] = {(double)info.products, (double)info.products32, (double)info.fallbacks, (double)info.cycles, info.ms[0], info.ms[3]};
+  std::copy(st, st + 6, kry_stats_);
+}
+
+void Kernel<double>::krylov_inner(KrylovInner p, double inner_rtol) {
+  if (p != KrylovInner::FP64 && p != KrylovInner::FP32) throw std::invalid_argument("krylov_inner: unknown precision");
+  if (!(inner_rtol > 0.) || !(inner_rtol < 1.)) throw std::invalid_argument("krylov_inner: inner_rtol must lie in (0, 1)");
+  inner_ = p;
+  inner_rtol_ = inner_rtol;
+}
+
+std::size_t Kernel<double>::krylov_prep_bytes() const {
+  if (inner_ != KrylovInner::FP32) return 0;
+  const long long b = hssk_kernel_matmul_f32_prep_bytes((long long)n(), int(d()));
+  if (b < 0) throw std::invalid_argument("krylov_inner: the FP32 inner product takes at most 64 coordinates");
+  return (std::size_t)b;
+}
+
+void Kernel<double>::krylov_prepare(const Model& M, KrylovWork& ws) const {
+  if (!ws.prep) return;
+  const hssk_kernel_spec spec{M.dX, (long long)n(), int(d()), device_type(), degree(), width(), lambda_};
+  ckk(hssk_kernel_matmul_f32_prep(M.ctx(), &spec, ws.prep, (long long)ws.prep_bytes));
 }
 
 // Stopwatches 4 / 5 / 6: products, solves, Krylov kernels (1 .. 3 belong to the variance loop this may run inside).
@@ -305,6 +336,9 @@ void Kernel<double>::krylov_block(const Model& M, KrylovWork& ws, int nc, double
   std::vector<char> conv(nc, 0);
   int steps = 0;
   bool first = true, all = false;
+  // mixed mode: the product inside the cycles in FP32 until a true residual fails to decrease
+  bool mixed = ws.prep != nullptr;
+  std::vector<double> rprev(nc, 0.), thr(nc, 0.);
   for (;;) {
     // 1. the true residual of every column
     hssk_watch_start(ctx, 4);
@@ -322,6 +356,13 @@ void Kernel<double>::krylov_block(const Model& M, KrylovWork& ws, int nc, double
       conv[c] = !(bn[c] > 0.) || nrm[c] <= rtol * bn[c];
       if (!conv[c]) active |= 1ULL << c;
     }
+    if (mixed && !first) {
+      bool stuck = false;
+      for (int c = 0; c < nc; c++) stuck = stuck || (!conv[c] && !(nrm[c] < rprev[c]));
+      if (stuck) { mixed = false; info.fallbacks++; }
+    }
+    if (mixed) rprev = nrm;
+    for (int c = 0; c < nc; c++) thr[c] = mixed ? std::max(rtol * bn[c], inner_rtol_ * nrm[c]) : rtol * bn[c];
     if (first) { res0 = res; first = false; }
     all = active == 0;
     if (all || steps >= maxit) break;
@@ -334,10 +375,17 @@ void Kernel<double>::krylov_block(const Model& M, KrylovWork& ws, int nc, double
       M.H.solve_device(nc, ws.Z, nn);
       hssk_watch_stop(ctx, 5);
       info.solves++;
-      hssk_watch_start(ctx, 4);
-      ckk(hssk_kernel_matmul(ctx, &spec, 0, ws.Z, nn, nc, ws.W, nn, 0));
-      hssk_watch_stop(ctx, 4);
-      info.products++;
+      if (mixed) {
+        hssk_watch_start(ctx, 7);
+        ckk(hssk_kernel_matmul_f32(ctx, &spec, ws.prep, ws.Z, nn, nc, ws.W, nn, 0, nullptr));
+        hssk_watch_stop(ctx, 7);
+        info.products32++;
+      } else {
+        hssk_watch_start(ctx, 4);
+        ckk(hssk_kernel_matmul(ctx, &spec, 0, ws.Z, nn, nc, ws.W, nn, 0));
+        hssk_watch_stop(ctx, 4);
+        info.products++;
+      }
       hssk_watch_start(ctx, 6);
       ckk(hssk_krylov_orth(ctx, ws.V, nn, nn, nc, k, ws.W, nn, active, ws.Hout, ldh));
       hssk_watch_stop(ctx, 6);
@@ -366,7 +414,7 @@ void Kernel<double>::krylov_block(const Model& M, KrylovWork& ws, int nc, double
         gc[k + 1] = -sc[k] * gc[k];
         gc[k] = cc[k] * gc[k];
         kc[c] = k + 1;
-        if (std::abs(gc[k + 1]) <= rtol * bn[c] || below == 0.) active &= ~(1ULL << c);
+        if (std::abs(gc[k + 1]) <= thr[c] || below == 0.) active &= ~(1ULL << c);
       }
       if (!active || steps >= maxit) break;
     }
@@ -410,7 +458,8 @@ KrylovInfo Kernel<double>::model_refine(double rtol, int maxit, int restart) {
   hssk_ctx* ctx = M.ctx();
   const long long nn = (long long)n();
   KrylovInfo info;
-  KrylovWork ws(ctx, nn, 1, maxit, restart, true);
+  KrylovWork ws(ctx, nn, 1, maxit, restart, true, krylov_prep_bytes());
+  krylov_prepare(M, ws);
   ckk(hssk_memcpy_h2d(ctx, ws.B, M.labels.data(), (long long)sizeof(double) * nn));
   ckk(hssk_memcpy_h2d(ctx, ws.X, M.weights.data(), (long long)sizeof(double) * nn));
   krylov_block(M, ws, 1, ws.X, ws.B, rtol, maxit, restart, info);
@@ -430,7 +479,8 @@ DenseMatrix<double> Kernel<double>::model_solve(const DenseMatrix<double>& B, Kr
   KrylovInfo local;
   DenseMatrix<double> X(n(), m);
   if (m > 0) {
-    KrylovWork ws(ctx, nn, std::min(m, CH), maxit, restart, true);
+    KrylovWork ws(ctx, nn, std::min(m, CH), maxit, restart, true, krylov_prep_bytes());
+    krylov_prepare(M, ws);
     for (int c0 = 0; c0 < m; c0 += CH) {
       const int nc = std::min(CH, m - c0);
       ckk(hssk_memcpy2d_h2d(ctx, ws.B, sizeof(double) * nn, B.ptr(0, c0), sizeof(double) * B.ld(), sizeof(double) * nn, nc));
@@ -1075,6 +1125,30 @@ int SPX_kernel_predict_variance_exact_double(STRUMPACKKernel K, int m, const dou
     krylov_info_out(I, info);
     return 0;
   } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_set_krylov_inner(STRUMPACKKernel K, int precision, double inner_rtol) {
+  try {
+    auto kr = static_cast<KernelRegression*>(K);
+    if (!kr || kr->precision != 0 || !kr->K || kr->K->device_type() < 0) return 1;
+    if (precision != 0 && precision != 1) return 1;
+    if (std::isnan(inner_rtol)) return 1;
+    kr->K->krylov_inner(precision ? kernel::KrylovInner::FP32 : kernel::KrylovInner::FP64,
+                        inner_rtol <= 0. ? kernel::KRYLOV_INNER_RTOL_DEFAULT : inner_rtol);
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_krylov_inner(STRUMPACKKernel K, int* precision, double* inner_rtol) {
+  auto kr = static_cast<KernelRegression*>(K);
+  if (!kr || kr->precision != 0 || !kr->K || kr->K->device_type() < 0) return 1;
+  if (precision) *precision = kr->K->krylov_inner() == kernel::KrylovInner::FP32 ? 1 : 0;
+  if (inner_rtol) *inner_rtol = kr->K->krylov_inner_rtol();
+  return 0;
+}
+int SPX_kernel_krylov_stats(STRUMPACKKernel K, double out[6]) {
+  auto k = model_of(K);
+  if (!k || !out || (k->device_type() != 0 && k->device_type() != 1)) return 1;
+  std::copy(k->krylov_stats(), k->krylov_stats() + 6, out);
+  return 0;
 }
 int SPX_kernel_krylov_ms(STRUMPACKKernel K, double out[3]) {
   auto k = model_of(K);

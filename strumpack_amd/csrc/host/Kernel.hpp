@@ -56,10 +56,16 @@ struct KrylovInfo {
   bool converged = true;                        // every column reached rtol
   int iterations = 0;                           // steps of the slowest column
   long long products = 0, solves = 0, cycles = 0;   // exact products, ULV solves and restart cycles, summed over the blocks
+  long long products32 = 0;                     // mixed mode: FP32 products inside the cycles (`products` then counts the FP64 ones alone)
+  long long fallbacks = 0;                      // mixed mode: blocks whose true residual did not decrease and went on in FP64
   std::vector<int> its;                         // per column: steps it took part in
   std::vector<double> residual, residual0;      // per column: ||b - (K + lambda I) x|| / ||b|| at the end and at the start (true ones)
-  double ms[3] = {0., 0., 0.};                  // device-clock milliseconds: products, solves, Krylov kernels
+  double ms[4] = {0., 0., 0., 0.};              // device-clock milliseconds: FP64 products, solves, Krylov kernels, FP32 products
 };
+
+// the precision of the product INSIDE the cycles of the exact solves (Kernel<double>::krylov_inner)
+enum class KrylovInner { FP64, FP32 };
+constexpr double KRYLOV_INNER_RTOL_DEFAULT = 1e-4;
 
 template <> class Kernel<double> {
   using scalar_t = double;
@@ -149,6 +155,19 @@ template <> class Kernel<double> {
                                                int restart = 30) const;
   // device-clock milliseconds of the last of these three calls: exact products, ULV solves, Krylov kernels (profiling)
   const double* krylov_ms() const { return kry_ms_; }
+  // ---- extension: mixed precision for these three calls.  Handle state, set like keep_model; FP64 is the default
+  // and leaves every call what it was, bit for bit.  With FP32 the product inside a cycle is hssk_kernel_matmul_f32 (FP32 per
+  // pair on the matrix cores, from float points prepared once per call); the product at a cycle's start -- the true residual,
+  // the only place where convergence is declared -- stays FP64.  A column leaves its cycle when the Arnoldi estimate is at most
+  // max(rtol ||b||, inner_rtol ||r||), r its true residual at the cycle's start: below the rounded operator's floor the estimate
+  // means nothing.  If a column's true residual does not decrease from one cycle start to the next, the rest of that block's
+  // call runs with the FP64 product (KrylovInfo::fallbacks; reported, not thrown).  inner_rtol must lie in (0, 1).  The calls
+  // then also throw for d > 64.
+  void krylov_inner(KrylovInner p, scalar_t inner_rtol = KRYLOV_INNER_RTOL_DEFAULT);
+  KrylovInner krylov_inner() const { return inner_; }
+  scalar_t krylov_inner_rtol() const { return inner_rtol_; }
+  // of the last of the three calls: FP64 products, FP32 products, fallbacks, cycles, ms of FP64 products, ms of FP32 products
+  const double* krylov_stats() const { return kry_stats_; }
 
   const DenseM_t& data() const { return data_; }
   DenseM_t& data() { return data_; }
@@ -181,7 +200,10 @@ template <> class Kernel<double> {
   bool keep_model_ = false;
   mutable double var_ms_[3] = {0., 0., 0.};
   mutable double grad_ms_[3] = {0., 0., 0.};
-  mutable double kry_ms_[3] = {0., 0., 0.};
+  mutable double kry_ms_[4] = {0., 0., 0., 0.};
+  mutable double kry_stats_[6] = {0., 0., 0., 0., 0., 0.};
+  KrylovInner inner_ = KrylovInner::FP64;
+  scalar_t inner_rtol_ = KRYLOV_INNER_RTOL_DEFAULT;
   const Model& model(const char* what) const;
   struct KrylovWork;   // the device blocks of a Krylov call (Kernel.cpp)
   const Model& krylov_model(const char* what, scalar_t rtol, int maxit, int restart) const;
@@ -189,6 +211,9 @@ template <> class Kernel<double> {
   void krylov_block(const Model& M, KrylovWork& ws, int nc, double* dX, const double* dB, scalar_t rtol, int maxit, int restart,
                     KrylovInfo& info) const;
   void krylov_finish(const Model& M, KrylovInfo& info) const;
+  // bytes of the prepared float points a call's work buffers carry (0 in FP64 mode), and their preparation
+  std::size_t krylov_prep_bytes() const;
+  void krylov_prepare(const Model& M, KrylovWork& ws) const;
   // the chunk loop of both variance calls; ws == nullptr: the compressed solve
   std::vector<scalar_t> variance_chunks(const Model& M, const DenseM_t& test, KrylovWork* ws, scalar_t rtol, int maxit, int restart,
                                         KrylovInfo* info) const;

@@ -15,8 +15,9 @@ KERNEL_SYMBOLS = [
     "SPX_kernel_variance_ms", "SPX_kernel_model_set_lambda", "SPX_kernel_model_write", "SPX_kernel_model_labels",
     "SPX_kernel_model_points", "SPX_kernel_lml_gradient", "SPX_kernel_model_probes", "SPX_kernel_model_residual",
     "SPX_kernel_gradient_ms", "SPX_kernel_model_refine", "SPX_kernel_model_solve", "SPX_kernel_predict_variance_exact_double",
-    "SPX_kernel_krylov_ms",
+    "SPX_kernel_krylov_ms", "SPX_kernel_set_krylov_inner", "SPX_kernel_krylov_inner", "SPX_kernel_krylov_stats",
 ]
+KRYLOV_INNER = {"f64": 0, "f32": 1}
 KERNEL_TYPES = {"Gauss": 0, "rbf": 0, "Laplace": 1, "ANOVA": 2}
 CLUSTERING = {"natural": 0, "2means": 1, "kdtree": 2, "pca": 3, "cobble": 4}
 
@@ -60,6 +61,9 @@ def load(path):
     L.SPX_kernel_model_solve.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp]
     L.SPX_kernel_predict_variance_exact_double.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, vp]
     L.SPX_kernel_krylov_ms.argtypes = [vp, vp]
+    L.SPX_kernel_set_krylov_inner.argtypes = [vp, C.c_int, C.c_double]
+    L.SPX_kernel_krylov_inner.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    L.SPX_kernel_krylov_stats.argtypes = [vp, vp]
     L.SPX_clustering.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int]
     L.SPX_clustering_device.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp]
     return L
@@ -111,10 +115,11 @@ class KernelRegression:
             raise RuntimeError("SPX_kernel_log_marginal_likelihood failed (no kept model)")
         return out.value
 
-    def predict_variance(self, T, exact=False, rtol=1e-8, maxit=100, restart=30, info=False):
+    def predict_variance(self, T, exact=False, rtol=1e-8, maxit=100, restart=30, info=False, inner=None, inner_rtol=None):
         """variance of the latent function at the rows of T (add lam for the observation noise); not clamped: the compressed
         matrix is K + lam I only up to the compression tolerance, so a value may be slightly negative.  exact=True: the solve
-        with the exact kernel matrix instead (see refine), up to rtol; info=True then also returns the dict of that solve"""
+        with the exact kernel matrix instead (see refine), up to rtol; info=True then also returns the dict of that solve;
+        inner / inner_rtol: see refine"""
         T = np.ascontiguousarray(T, dtype=np.float64)
         out = np.zeros(T.shape[0])
         if not exact:
@@ -122,35 +127,87 @@ class KernelRegression:
                 raise RuntimeError("SPX_kernel_predict_variance_double failed (no kept model)")
             return out
         buf = np.zeros(8 + 2 * T.shape[0])
-        if self.L.SPX_kernel_predict_variance_exact_double(self.K, T.shape[0], T.ctypes.data, out.ctypes.data, float(rtol), int(maxit),
-                                                           int(restart), buf.ctypes.data):
-            raise RuntimeError("SPX_kernel_predict_variance_exact_double failed (a kept model of a Gauss or Laplace fit and valid "
-                               "rtol / maxit / restart are needed)")
-        return (out, self._krylov_info(buf)) if info else out
+        with self._inner(inner, inner_rtol):
+            if self.L.SPX_kernel_predict_variance_exact_double(self.K, T.shape[0], T.ctypes.data, out.ctypes.data, float(rtol), int(maxit),
+                                                               int(restart), buf.ctypes.data):
+                raise RuntimeError("SPX_kernel_predict_variance_exact_double failed (a kept model of a Gauss or Laplace fit and valid "
+                                   "rtol / maxit / restart are needed; inner=\"f32\": at most 64 coordinates)")
+            return (out, self._krylov_stats(self._krylov_info(buf))) if info else out
+
+    # ---- the precision of the product inside the cycles of refine / solve / predict_variance(exact=True) ----
+    def set_krylov_inner(self, inner="f64", inner_rtol=None):
+        """handle state, like keep_model: "f64" (the default) or "f32" -- the FP32 matrix-core product inside the restart cycles,
+        FP64 true residuals at their starts; inner_rtol in (0, 1) (None: the library's default, 1e-4): a column leaves its cycle at
+        max(rtol ||b||, inner_rtol ||r at the cycle's start||)"""
+        if inner not in KRYLOV_INNER:
+            raise ValueError('inner must be "f64" or "f32"')
+        if inner_rtol is not None and not 0.0 < float(inner_rtol) < 1.0:      # (also not-a-number)
+            raise RuntimeError("inner_rtol must lie in (0, 1)")
+        if self.L.SPX_kernel_set_krylov_inner(self.K, KRYLOV_INNER[inner], 0.0 if inner_rtol is None else float(inner_rtol)):
+            raise RuntimeError("SPX_kernel_set_krylov_inner failed (a double handle with a built-in kernel is needed)")
+        return self
+
+    def krylov_inner(self):
+        """(inner, inner_rtol) as set"""
+        p, r = C.c_int(0), C.c_double(0.0)
+        if self.L.SPX_kernel_krylov_inner(self.K, C.byref(p), C.byref(r)):
+            raise RuntimeError("SPX_kernel_krylov_inner failed (a double handle with a built-in kernel is needed)")
+        return ("f32" if p.value else "f64"), r.value
+
+    def _inner(self, inner, inner_rtol):
+        """context: the mode of one call.  inner=None: the handle's own mode (set_krylov_inner; "f64" unless set); "f64" / "f32"
+        force that precision for this call whatever the handle says; inner_rtol=None: the handle's.  The handle's mode is
+        restored afterwards."""
+        kr = self
+
+        class Mode:
+            def __enter__(self):
+                self.old = None
+                if inner is not None or inner_rtol is not None:
+                    self.old = kr.krylov_inner()
+                    kr.set_krylov_inner(self.old[0] if inner is None else inner, self.old[1] if inner_rtol is None else inner_rtol)
+
+            def __exit__(self, *exc):
+                if self.old is not None:
+                    kr.set_krylov_inner(*self.old)
+                return False
+        return Mode()
+
+    def _krylov_stats(self, d):
+        """the counts of the last call that the 8 + 2 m info doubles have no room for"""
+        st = np.zeros(6)
+        if self.L.SPX_kernel_krylov_stats(self.K, st.ctypes.data) == 0:
+            d["products32"], d["fallbacks"] = int(st[1]), int(st[2])
+        return d
 
     @staticmethod
     def _krylov_info(buf):
         m = int(buf[7])
         return dict(converged=bool(buf[0]), iterations=int(buf[1]), products=int(buf[2]), solves=int(buf[3]), cycles=int(buf[4]),
                     residual0=float(buf[5]), residual_max=float(buf[6]), residual=buf[8:8 + m].copy(),
-                    its=buf[8 + m:8 + 2 * m].astype(np.int64))
+                    its=buf[8 + m:8 + 2 * m].astype(np.int64), products32=0, fallbacks=0)
 
-    def refine(self, rtol=1e-8, maxit=100, restart=30):
+    def refine(self, rtol=1e-8, maxit=100, restart=30, inner=None, inner_rtol=None):
         """weights of the EXACT K + lam I: restarted GMRES on the device with the kept factors as preconditioner, from the
         current weights.  weights(), decision_function, fit_residual and log_marginal_likelihood follow; logabsdet stays that of
         the compressed matrix.  Returns a dict: converged, iterations, products, solves, cycles, residual0 (before), residual
-        (after; both true relative residuals), its.  Not converging within maxit steps is reported, not raised."""
+        (after; both true relative residuals), its, products32, fallbacks.  Not converging within maxit steps is reported, not
+        raised.  inner=None runs in the handle's mode (set_krylov_inner; FP64 unless set), "f64" and "f32" force the precision of
+        this call.  inner="f32": the product inside the cycles is the FP32
+        matrix-core one, `products` counts the FP64 products alone (one per cycle start), `products32` the others, `fallbacks`
+        the blocks that went back to FP64 because a true residual did not decrease; inner_rtol: see set_krylov_inner."""
         buf = np.zeros(10)
-        if self.L.SPX_kernel_model_refine(self.K, float(rtol), int(maxit), int(restart), buf.ctypes.data):
-            raise RuntimeError("SPX_kernel_model_refine failed (a kept model of a Gauss or Laplace fit and valid rtol / maxit / restart "
-                               "are needed)")
-        d = self._krylov_info(buf)
+        with self._inner(inner, inner_rtol):
+            if self.L.SPX_kernel_model_refine(self.K, float(rtol), int(maxit), int(restart), buf.ctypes.data):
+                raise RuntimeError("SPX_kernel_model_refine failed (a kept model of a Gauss or Laplace fit and valid rtol / maxit / restart "
+                                   "are needed; inner=\"f32\": at most 64 coordinates)")
+        d = self._krylov_stats(self._krylov_info(buf))
         d["residual"] = float(d["residual"][0])
         d["its"] = int(d["its"][0])
         del d["residual_max"]
         return d
 
-    def solve(self, B, rtol=1e-8, maxit=100, restart=30):
+    def solve(self, B, rtol=1e-8, maxit=100, restart=30, inner=None, inner_rtol=None):
         """(X, dict) with (K + lam I) X = B for the exact kernel matrix; B: n or n x m, rows in cluster order (the order of
         model_points()).  The model is not changed.  residual and its of the dict are per column."""
         B = np.asarray(B, dtype=np.float64)
@@ -160,11 +217,12 @@ class KernelRegression:
             raise ValueError("solve: B must have n rows")
         m = B.shape[1]
         X, buf = np.zeros((self.n, m), order="F"), np.zeros(8 + 2 * m)
-        if self.L.SPX_kernel_model_solve(self.K, m, B.ctypes.data, self.n, X.ctypes.data, self.n, float(rtol), int(maxit), int(restart),
-                                         buf.ctypes.data):
-            raise RuntimeError("SPX_kernel_model_solve failed (a kept model of a Gauss or Laplace fit and valid rtol / maxit / restart "
-                               "are needed)")
-        return (X[:, 0] if one else X), self._krylov_info(buf)
+        with self._inner(inner, inner_rtol):
+            if self.L.SPX_kernel_model_solve(self.K, m, B.ctypes.data, self.n, X.ctypes.data, self.n, float(rtol), int(maxit), int(restart),
+                                             buf.ctypes.data):
+                raise RuntimeError("SPX_kernel_model_solve failed (a kept model of a Gauss or Laplace fit and valid rtol / maxit / restart "
+                                   "are needed; inner=\"f32\": at most 64 coordinates)")
+        return (X[:, 0] if one else X), self._krylov_stats(self._krylov_info(buf))
 
     def krylov_ms(self):
         out = np.zeros(3)
