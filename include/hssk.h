@@ -226,7 +226,13 @@ int hssk_leaf_update_vbatched(hssk_ctx* ctx, const hssk_leaf_update_desc* descs,
 /* ---- kernel matrices ---------------------------------------------------------- */
 /* A kernel matrix K(i, j) = k(x_i, x_j) + lambda [i == j] over n points x_i in R^d stored one point per column
  * (d x n, column-major, device).  type 0: Gauss exp(-|x-y|_2^2 / (2 h^2)), 1: Laplace exp(-|x-y|_1 / h),
- * 2: ANOVA of degree p <= 8   (kernel/Kernel.hpp:333-399; eval :122-125). */
+ * 2: ANOVA of degree p <= 8   (kernel/Kernel.hpp:333-399; eval :122-125).  Extension: the Matern kernels over the
+ * Euclidean distance r, with s = sqrt(2 nu) r / h -- type 3: Matern32, (1 + s) e^-s, nu = 3/2; type 4: Matern52,
+ * (1 + s + s^2 / 3) e^-s, nu = 5/2 -- evaluated from the squared distance (the Gauss distance loop, then
+ * csrc/kernels/hssk_matern.h); a pair at distance 0 gives exactly 1.  Types 3 and 4 are taken by the sums and products over all
+ * pairs -- hssk_kernel_predict, hssk_kernel_cross, hssk_kernel_predict_cols, hssk_kernel_matmul, hssk_kernel_matmul_f32 (and its
+ * prep), hssk_matern_predict_f32 (and _wide) -- at any d those take.  The construction kernels (hssk_kernel_eval_vbatched,
+ * hssk_gram_gen_vbatched) and with them the kernel ridge regression fit do NOT take them yet: they return 2 and write nothing. */
 typedef struct hssk_kernel_spec {
   const double* X;
   long long n;
@@ -308,6 +314,17 @@ int hssk_kernel_predict_f32(hssk_ctx* ctx, const float* X, long long n, int d, i
  * d >= 65 the route rule above admits only tiles whose exponents are below ~7. */
 int hssk_kernel_predict_f32_wide(hssk_ctx* ctx, const float* X, long long n, int d, int type, int p, double h,
                                  const float* w, const float* T, int m, float* pred, long long* stats);
+/* The two sums above for the Matern kernels, twice_nu = 3 (Matern32) or 5 (Matern52), anything else refused: d <= 64 and
+ * d >= 65.  (Entry points of their own: the two above take the type codes 0 .. 2 of the reference and refuse every other one.)
+ * Arguments, grid, sums, their order and the statistics are those of hssk_kernel_predict_f32 / _wide.  Up to 64 coordinates
+ * both routes exist: the points are scaled by sqrt(2 nu) / h, so that the matrix-core accumulator is u = s^2, the value is
+ * polynomial(s) exp2(-s log2 e) with s = sqrt(max(u, 0)) -- the clamp keeps near-duplicate points, where cancellation makes u
+ * negative, finite -- and the route rule is the one above with HSSK_KPREDICT_TAU, read on these scaled points (|dk/du| <= 1/2:
+ * an error in u costs a Matern term no more than it costs a Gauss term). */
+int hssk_matern_predict_f32(hssk_ctx* ctx, const float* X, long long n, int d, int twice_nu, double h, const float* w,
+                            const float* T, int m, float* pred, long long* stats);
+int hssk_matern_predict_f32_wide(hssk_ctx* ctx, const float* X, long long n, int d, int twice_nu, double h, const float* w,
+                                 const float* T, int m, float* pred, long long* stats);
 /* splits of the training set hssk_kernel_predict_f32 (and _wide) takes for n training and m test points: a function of (n, m) alone */
 int hssk_kernel_predict_splits(long long n, int m);
 
@@ -852,8 +869,9 @@ int hssk_logabsdet_vbatched(hssk_ctx* ctx, const hssk_logdet_desc* descs, int co
 /* out(i, c) = sum_r g(x_i, x_r) B(r, c), i, r < n over the spec's own points, c < nc, 1 <= nc <= 64: the product of the EXACT
  * kernel matrix with a block of vectors, the matrix never stored.  B and out: device, column-major, ldb, ldo >= n, out may not
  * alias B; the rows n .. ldo - 1 of out are not touched.  deriv = 0: g = k, spec->lambda added on the diagonal (the product with
- * K + lambda I); deriv = 1: g = dk/dh = k |x - y|_2^2 / h^3 (Gauss), k |x - y|_1 / h^2 (Laplace), the diagonal exactly 0.  Gauss
- * and Laplace, any d >= 1 (beyond 64 coordinates the points pass through the LDS 32 coordinates at a time); ANOVA returns
+ * K + lambda I); deriv = 1: g = dk/dh = k |x - y|_2^2 / h^3 (Gauss), k |x - y|_1 / h^2 (Laplace), s^2 e^-s / h
+ * (Matern32), s^2 (1 + s) e^-s / (3 h) (Matern52; neither divides by the distance), the diagonal exactly 0.  Gauss, Laplace
+ * and Matern, any d >= 1 (beyond 64 coordinates the points pass through the LDS 32 coordinates at a time); ANOVA returns
  * HSSK_UNSUPPORTED.  The grid is (tiles of 64 rows) x (splits of the training points): splits = 0 takes
  * hssk_kernel_matmul_splits(n), a positive value forces the count (at most one split per 16 training points).  Split partials
  * go to slabs the context keeps and are added in split order (hssk_sum_slabs): no atomics, bitwise repeatable.  n = 0 or nc = 0:
@@ -871,12 +889,12 @@ int hssk_kernel_matmul_splits(long long n);   /* what splits = 0 chooses: a func
 long long hssk_kernel_matmul_f32_prep_bytes(long long n, int d);
 /* The points of spec (FP64, device) centred in FP64 (the mean in a fixed order), scaled, rounded once to float and laid out for
  * hssk_kernel_matmul_f32 in `prep` (device, at least hssk_kernel_matmul_f32_prep_bytes): once per point set and width, not per
- * product.  Gauss and Laplace, d <= 64; anything else returns HSSK_UNSUPPORTED (2) and writes nothing. */
+ * product.  Gauss, Laplace and Matern (scale sqrt(2 nu) / h), d <= 64; anything else returns HSSK_UNSUPPORTED (2) and writes nothing. */
 int hssk_kernel_matmul_f32_prep(hssk_ctx* ctx, const hssk_kernel_spec* spec, void* prep, long long bytes);
 /* out(i, c) = sum_r k32(x_i, x_r) B(r, c) + spec->lambda B(i, c), 1 <= nc <= 64: B and out are FP64 blocks as for
  * hssk_kernel_matmul (column-major, ldb, ldo >= n, no aliasing, rows n .. ld - 1 never touched); B is rounded to float as it is
- * staged.  k32: FP32 from the prepared points -- Gauss tiles under HSSK_KMATMUL_F32_TAU on the matrix cores (norm expansion over
- * K = d + 2, exp2), every other tile in the FP32 difference form; the pair r == i is exactly 1.  g times B on the FP32 matrix
+ * staged.  k32: FP32 from the prepared points -- Gauss and Matern tiles under HSSK_KMATMUL_F32_TAU on the matrix cores (norm expansion
+ * over K = d + 2, then exp2, for Matern the clamped square root and polynomial(s) exp2(-s log2 e)), every other tile in the FP32 difference form; the pair r == i is exactly 1.  g times B on the FP32 matrix
  * cores, no FP32 sum longer than 64 training points, FP64 across chunks and splits; lambda B(i, c) in FP64 from the unrounded B.
  * Grid and splits as for hssk_kernel_matmul (splits = 0: hssk_kernel_matmul_f32_splits(n); at most one split per 64 training
  * points).  No atomics on results: bitwise repeatable, and a column does not depend on the other columns.  ANOVA and d > 64 return

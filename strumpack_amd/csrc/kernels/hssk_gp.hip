@@ -57,7 +57,11 @@ int gp_launch(hssk_ctx* ctx, const char* who, const hssk_kernel_spec* spec, cons
     return 2;
   }
   const dim3 grid((unsigned)((m + PR_T - 1) / PR_T));
-  if (!wide) HSSK_LAUNCH((kernel_predict_kernel<MODE>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, ldw, T, m, out, ldo);
+  const bool matern = spec->type >= 3;
+  if (!wide && matern) HSSK_LAUNCH((kernel_predict_kernel<MODE, true>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, ldw, T, m, out, ldo);
+  else if (!wide) HSSK_LAUNCH((kernel_predict_kernel<MODE>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, ldw, T, m, out, ldo);
+  else if (spec->type == 3) HSSK_LAUNCH((kernel_predict_wide_kernel<3, 32, MODE>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, ldw, T, m, out, ldo);
+  else if (spec->type == 4) HSSK_LAUNCH((kernel_predict_wide_kernel<4, 32, MODE>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, ldw, T, m, out, ldo);
   else if (spec->type == 0) HSSK_LAUNCH((kernel_predict_wide_kernel<0, 32, MODE>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, ldw, T, m, out, ldo);
   else if (spec->type == 1) HSSK_LAUNCH((kernel_predict_wide_kernel<1, 32, MODE>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, ldw, T, m, out, ldo);
   else HSSK_LAUNCH((kernel_predict_wide_kernel<2, 8, MODE>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, ldw, T, m, out, ldo);

@@ -410,6 +410,7 @@ extern "C" int hssk_kernel_eval_vbatched(hssk_ctx* ctx, const hssk_kernel_spec* 
   HSSK_API_BEGIN
   if (count <= 0) return 0;
   check_spec(*spec);
+  if (spec->type >= 3) HSSK_UNSUPPORTED("Gauss / Laplace / ANOVA kernels only (the Matern kernels have sums and products, no construction)");
   std::vector<KTile> tiles;
   for (int p = 0; p < count; p++)
     for (int tc = 0; tc * KE_T < descs[p].nc; tc++)
@@ -1061,7 +1062,10 @@ extern "C" int hssk_kernel_predict(hssk_ctx* ctx, const hssk_kernel_spec* spec, 
   check_spec(*spec);
   const dim3 grid((unsigned)((m + PR_T - 1) / PR_T));
   const size_t z = 0;
-  if (spec->d <= PR_DMAX) HSSK_LAUNCH((kernel_predict_kernel<PR_SUM>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);
+  if (spec->d <= PR_DMAX && spec->type >= 3) HSSK_LAUNCH((kernel_predict_kernel<PR_SUM, true>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);
+  else if (spec->d <= PR_DMAX) HSSK_LAUNCH((kernel_predict_kernel<PR_SUM>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);
+  else if (spec->type == 3) HSSK_LAUNCH((kernel_predict_wide_kernel<3, 32, PR_SUM>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);
+  else if (spec->type == 4) HSSK_LAUNCH((kernel_predict_wide_kernel<4, 32, PR_SUM>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);
   else if (spec->type == 0) HSSK_LAUNCH((kernel_predict_wide_kernel<0, 32, PR_SUM>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);
   else if (spec->type == 1) HSSK_LAUNCH((kernel_predict_wide_kernel<1, 32, PR_SUM>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);
   else HSSK_LAUNCH((kernel_predict_wide_kernel<2, 8, PR_SUM>), grid, dim3(PR_T), 0, ctx->stream, *spec, w, z, T, m, pred, z);

@@ -5,6 +5,8 @@
 //   out(i, c) = sum_r g(x_i, x_r) B(r, c)      g = k (+ lambda on the diagonal)                         deriv = 0
 //                                              g = dk/dh = k a c_h, a the exponent's magnitude,         deriv = 1
 //                                                  c_h = 2 / h (Gauss), 1 / h (Laplace)
+//                                              the Matern kernels (TYPE 3 and 4): value and derivative are the finish of
+//                                                  hssk_matern.h on the Gauss distance
 //
 // Tiling.  The grid is (tiles of 64 output rows) x (splits of the training points).  A workgroup of four waves owns a tile; wave w
 // keeps the 16 rows 16 w .. 16 w + 15 against all 64 columns in four hssk_d4 accumulators (32 registers).  The training points
@@ -67,6 +69,7 @@ __global__ __launch_bounds__(KM_T) void kmatmul_kernel(hssk_kernel_spec ks, cons
   double* o = out + (size_t)blockIdx.y * slab;
   const double scale = TYPE == 0 ? -1. / (2. * ks.h * ks.h) : -1. / ks.h;
   const double ch = TYPE == 0 ? 2. / ks.h : 1. / ks.h;
+  const double mc = hssk_matern_c(TYPE, ks.h);   // (TYPE 3 and 4 only)
   // entries of a stage this thread evaluates / fetches: training point kt against the rows (columns of B) it + 16 q
   const int kt = tid & 15, it = tid >> 4;
   hssk_d4 acc[4];
@@ -98,10 +101,15 @@ __global__ __launch_bounds__(KM_T) void kmatmul_kernel(hssk_kernel_spec ks, cons
   };
   // a distance -> an entry of g, straight into the stage buffer Sg (a training point past the split's end: selected to be 0)
   auto finish = [&](long long k0, int q, double a, double* Sg) {
-    const double e = a * scale;
-    double v = exp(e);
-    if (DERIV) v = v * -e * ch;
-    else if (i0 + it + 16 * q == k0 + kt) v += ks.lambda;
+    double v;
+    if (TYPE >= 3) {
+      v = hssk_matern<TYPE >= 3 ? TYPE : 3, DERIV>(a, mc, ks.h);
+    } else {
+      const double e = a * scale;
+      v = exp(e);
+      if (DERIV) v = v * -e * ch;
+    }
+    if (!DERIV && i0 + it + 16 * q == k0 + kt) v += ks.lambda;
     Sg[(it + 16 * q) * KM_KP + kt] = k0 + kt < re ? v : 0.;
   };
   // the entries of stage k0 into Sg.  Whole points: one entry at a time (one exponential in flight: the loop is kept rolled, so
@@ -115,7 +123,7 @@ __global__ __launch_bounds__(KM_T) void kmatmul_kernel(hssk_kernel_spec ks, cons
         double a = 0.;
         for (int j = 0; j < d; j++) {
           const double df = xi[j] - xr[j];
-          a += TYPE == 0 ? df * df : fabs(df);
+          a += TYPE == 1 ? fabs(df) : df * df;
         }
         finish(k0, q, a, Sg);
       }
@@ -138,7 +146,7 @@ __global__ __launch_bounds__(KM_T) void kmatmul_kernel(hssk_kernel_spec ks, cons
 #pragma unroll
           for (int q = 0; q < 4; q++) {
             const double df = Xi[(it + 16 * q) * dp + j] - t;
-            a[q] += TYPE == 0 ? df * df : fabs(df);
+            a[q] += TYPE == 1 ? fabs(df) : df * df;
           }
         }
       }
@@ -239,7 +247,7 @@ extern "C" int hssk_kernel_matmul(hssk_ctx* ctx, const hssk_kernel_spec* spec, i
   if (splits < 0) throw std::invalid_argument("hssk_kernel_matmul: negative split count");
   if (spec->n == 0 || nc == 0) return 0;
   check_spec(*spec);
-  if (spec->type == 2) HSSK_UNSUPPORTED("Gauss / Laplace kernels only (no ANOVA derivative, no ANOVA product)");
+  if (spec->type == 2) HSSK_UNSUPPORTED("Gauss / Laplace / Matern kernels only (no ANOVA derivative, no ANOVA product)");
   if (!B || !out) throw std::invalid_argument("hssk_kernel_matmul: null pointer");
   if (ldb < spec->n || ldo < spec->n) throw std::invalid_argument("hssk_kernel_matmul: leading dimension below the point count");
   if (B == out) throw std::invalid_argument("hssk_kernel_matmul: out may not alias B");
@@ -272,7 +280,15 @@ extern "C" int hssk_kernel_matmul(hssk_ctx* ctx, const hssk_kernel_spec* spec, i
     case 4: km_launch<1, 0, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
     case 5: km_launch<1, 0, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
     case 6: km_launch<1, 1, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    default: km_launch<1, 1, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
+    case 7: km_launch<1, 1, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
+    case 12: km_launch<3, 0, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
+    case 13: km_launch<3, 0, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
+    case 14: km_launch<3, 1, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
+    case 15: km_launch<3, 1, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
+    case 16: km_launch<4, 0, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
+    case 17: km_launch<4, 0, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
+    case 18: km_launch<4, 1, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
+    default: km_launch<4, 1, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
   }
   hssk_rt::check_launch();
   if (s > 1) {

@@ -5,7 +5,8 @@
 //   out(i, c) = sum_r k32(x_i, x_r) B(r, c) + lambda B(i, c)         B, out: the solver's FP64 blocks
 //
 // Points (hssk_kernel_matmul_f32_prep, once per call of the solver).  The FP64 points are centred in FP64 (kmf_mean_kernel: the
-// mean in a fixed order), scaled by s (Gauss: s^2 = log2(e) / (2 h^2); Laplace: s = log2(e) / h) and rounded ONCE to float.  They
+// mean in a fixed order), scaled by s (Gauss: s^2 = log2(e) / (2 h^2); Laplace: s = log2(e) / h; Matern: s = sqrt(2 nu) / h) and
+// rounded ONCE to float.  They
 // are kept coordinate by coordinate (row j of Pa is coordinate j of every point, ldn = n rounded up to 64) in the augmented form
 // of the prediction kernel: rows 0 .. d-1: -2 x~, row d: |x~|^2 (of the rounded x~, in FP64, rounded once), row d + 1: 1, zeros up
 // to the 2 KSM rows the matrix-core route reads; padding points are all zero.  x~ itself is -0.5 times a row: exact.  tmax[t]:
@@ -17,13 +18,16 @@
 // the other buffer and fetch its B entries into registers -- one barrier per stage, as in hssk_kmatmul.hip.
 //
 // The kernel values of a stage go one of two routes, the same for the whole workgroup:
-//   * matrix cores (Gauss only): wave w takes the 32 training points 32 (w >> 1) .. against the 32 rows 32 (w & 1) ..; the
+//   * matrix cores (Gauss, Matern): wave w takes the 32 training points 32 (w >> 1) .. against the 32 rows 32 (w & 1) ..; the
 //     base-2 exponent |x~_r|^2 + |x~_i|^2 - 2 x~_r . x~_i is the accumulator of KSM v_mfma_f32_32x32x2_f32 over K = d + 2 (training
 //     points along M, rows along N = the lane), then exp2.  Taken iff 4 (d + 4) 2^-24 (tmax[row tile] + tmax[training tile]), the
 //     worst error the norm expansion can cause in an exponent, is at most HSSK_KMATMUL_F32_TAU;
 //   * difference form (Laplace, and the Gauss stages the rule refuses): lane = row, wave w takes the training points 16 w ..
 //     16 w + 15, whose coordinates arrive through uniform loads; FP32 differences, the coordinates in order, then exp2.
 // The pair r == i is SELECTED to be 1 and a training point past the split's end to be 0, whatever was evaluated.
+// The Matern kernels (TYPE 3 and 4) take both routes under the same rule and threshold: with their scale the
+// accumulator -- of the matrix cores or of the differences -- is u = s^2, and exp2 gives way to hssk_matern_f32(u), whose clamp
+// max(u, 0) in front of the square root keeps near-duplicate points, where cancellation makes u negative, finite.
 //
 // The product is taken transposed (A operand: the B stage, columns along M; B operand: g, rows along N = the lane), wave w owning
 // the 32 rows 32 (w & 1) .. against the 32 columns 32 (w >> 1) ..: 32 MFMAs per stage into a cleared FP32 accumulator, which is
@@ -34,6 +38,7 @@
 #include "hssk_device.h"
 #include "hssk_internal.h"
 #include "hssk_kpair.h"
+#include "hssk_matern.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -136,7 +141,7 @@ __global__ __launch_bounds__(256) void kmf_main_kernel(KfArgs a) {
   double* o = a.out + (size_t)blockIdx.y * a.slab;
   // the rows of this wave as the second operand of the exponent MFMAs: x~ | 1 | |x~|^2
   float bq[KSM];
-  if (TYPE == 0) {
+  if (TYPE != 1) {
 #pragma unroll
     for (int s = 0; s < KSM; s++) {
       const int c = 2 * s + half;
@@ -144,7 +149,7 @@ __global__ __launch_bounds__(256) void kmf_main_kernel(KfArgs a) {
       bq[s] = c < d ? -0.5f * Pa[(size_t)c * ldn + at] : (c == d ? Pa[(size_t)(d + 1) * ldn + at] : (c == d + 1 ? Pa[(size_t)d * ldn + at] : 0.f));
     }
   }
-  const double tm = TYPE == 0 ? (double)a.tmax[blockIdx.x] : 0.;
+  const double tm = TYPE != 1 ? (double)a.tmax[blockIdx.x] : 0.;
   const double rule = 4. * (d + 4) * 5.9604644775390625e-8;   // 4 (d + 4) 2^-24
   long long nmf = 0, ndf = 0;
   double dacc[16];
@@ -171,7 +176,7 @@ __global__ __launch_bounds__(256) void kmf_main_kernel(KfArgs a) {
   constexpr bool PRE = KSM <= 9;
   float xa[PRE ? KSM : 1];
   auto route = [&](int k0) {
-    const bool mf = TYPE == 0 && rule * (tm + (double)a.tmax[k0 / KF_T]) <= HSSK_KMATMUL_F32_TAU;
+    const bool mf = TYPE != 1 && rule * (tm + (double)a.tmax[k0 / KF_T]) <= HSSK_KMATMUL_F32_TAU;
     if (PRE && mf) {
 #pragma unroll
       for (int s = 0; s < KSM; s++) xa[PRE ? s : 0] = Pa[(size_t)(2 * s + half) * ldn + (size_t)k0 + 32 * hblk + l32];
@@ -193,7 +198,7 @@ __global__ __launch_bounds__(256) void kmf_main_kernel(KfArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const int kk = 32 * hblk + 8 * (r / 4) + 4 * half + (r % 4);
-        float v = exp2f(-fmaxf(e[r], 0.f));
+        float v = TYPE >= 3 ? hssk_matern_f32<TYPE >= 3 ? TYPE : 3>(e[r]) : exp2f(-fmaxf(e[r], 0.f));
         if (k0 + kk == i0 + row) v = 1.f;
         Sg[kk * KF_T + row] = k0 + kk < re ? v : 0.f;
       }
@@ -211,13 +216,13 @@ __global__ __launch_bounds__(256) void kmf_main_kernel(KfArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; r++) {
           const float df = -0.5f * xb[r] - t;
-          acc[r] += TYPE == 0 ? df * df : fabsf(df);
+          acc[r] += TYPE == 1 ? fabsf(df) : df * df;
         }
       }
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const int kk = 16 * wv + r;
-        float v = exp2f(-acc[r]);
+        float v = TYPE >= 3 ? hssk_matern_f32<TYPE >= 3 ? TYPE : 3>(acc[r]) : exp2f(-acc[r]);
         if (k0 + kk == i0 + lane) v = 1.f;
         Sg[kk * KF_T + lane] = k0 + kk < re ? v : 0.f;
       }
@@ -318,7 +323,7 @@ extern "C" long long hssk_kernel_matmul_f32_prep_bytes(long long n, int d) {
 extern "C" int hssk_kernel_matmul_f32_prep(hssk_ctx* ctx, const hssk_kernel_spec* spec, void* prep, long long bytes) {
   HSSK_API_BEGIN
   kmf_check_spec("hssk_kernel_matmul_f32_prep", ctx, spec);
-  if (spec->type == 2) HSSK_UNSUPPORTED("Gauss / Laplace kernels only (no ANOVA product)");
+  if (spec->type == 2) HSSK_UNSUPPORTED("Gauss / Laplace / Matern kernels only (no ANOVA product)");
   if (spec->d > KF_DMAX) HSSK_UNSUPPORTED("at most 64 coordinates");
   if (spec->n == 0) return 0;
   const KfLayout L = kf_layout(spec->n, spec->d);
@@ -326,7 +331,8 @@ extern "C" int hssk_kernel_matmul_f32_prep(hssk_ctx* ctx, const hssk_kernel_spec
   if (bytes < (long long)L.total) throw std::invalid_argument("hssk_kernel_matmul_f32_prep: the buffer is smaller than hssk_kernel_matmul_f32_prep_bytes");
   char* base = (char*)prep;
   const double l2e = 1.4426950408889634;
-  const double scale = spec->type == 1 ? l2e / spec->h : std::sqrt(l2e) / (spec->h * std::sqrt(2.));
+  const double scale = spec->type >= 3 ? std::sqrt(spec->type == 3 ? 3. : 5.) / spec->h
+                                       : (spec->type == 1 ? l2e / spec->h : std::sqrt(l2e) / (spec->h * std::sqrt(2.)));
   HSSK_LAUNCH(kmf_mean_kernel, dim3(KF_G), dim3(256), 0, ctx->stream, spec->X, spec->d, spec->n, (double*)(base + L.o_pm));
   HSSK_LAUNCH(kmf_prep_kernel, dim3((unsigned)L.nt), dim3(64), 0, ctx->stream, spec->X, spec->n, spec->d, L.kp, scale,
               (const double*)(base + L.o_pm), (float*)(base + L.o_pa), L.ldn, (float*)(base + L.o_tm));
@@ -338,7 +344,7 @@ extern "C" int hssk_kernel_matmul_f32(hssk_ctx* ctx, const hssk_kernel_spec* spe
                                       double* out, long long ldo, int splits, long long* stats) {
   HSSK_API_BEGIN
   kmf_check_spec("hssk_kernel_matmul_f32", ctx, spec);
-  if (spec->type == 2) HSSK_UNSUPPORTED("Gauss / Laplace kernels only (no ANOVA product)");
+  if (spec->type == 2) HSSK_UNSUPPORTED("Gauss / Laplace / Matern kernels only (no ANOVA product)");
   if (spec->d > KF_DMAX) HSSK_UNSUPPORTED("at most 64 coordinates");
   if (nc < 1 || nc > 64) throw std::invalid_argument("hssk_kernel_matmul_f32: between 1 and 64 columns at a time");
   if (splits < 0) throw std::invalid_argument("hssk_kernel_matmul_f32: negative split count");
@@ -377,7 +383,19 @@ extern "C" int hssk_kernel_matmul_f32(hssk_ctx* ctx, const hssk_kernel_spec* spe
   }
   const int ksm = kf_ksm(spec->d);
   if (spec->type == 1) kmf_launch<1, 1>(ctx, a, (int)s);
-  else if (ksm == 2) kmf_launch<0, 2>(ctx, a, (int)s);
+  else if (spec->type == 3) {
+    if (ksm == 2) kmf_launch<3, 2>(ctx, a, (int)s);
+    else if (ksm == 5) kmf_launch<3, 5>(ctx, a, (int)s);
+    else if (ksm == 9) kmf_launch<3, 9>(ctx, a, (int)s);
+    else if (ksm == 17) kmf_launch<3, 17>(ctx, a, (int)s);
+    else kmf_launch<3, 33>(ctx, a, (int)s);
+  } else if (spec->type == 4) {
+    if (ksm == 2) kmf_launch<4, 2>(ctx, a, (int)s);
+    else if (ksm == 5) kmf_launch<4, 5>(ctx, a, (int)s);
+    else if (ksm == 9) kmf_launch<4, 9>(ctx, a, (int)s);
+    else if (ksm == 17) kmf_launch<4, 17>(ctx, a, (int)s);
+    else kmf_launch<4, 33>(ctx, a, (int)s);
+  } else if (ksm == 2) kmf_launch<0, 2>(ctx, a, (int)s);
   else if (ksm == 5) kmf_launch<0, 5>(ctx, a, (int)s);
   else if (ksm == 9) kmf_launch<0, 9>(ctx, a, (int)s);
   else if (ksm == 17) kmf_launch<0, 17>(ctx, a, (int)s);

@@ -11,6 +11,7 @@
 #pragma once
 #include "hssk_device.h"
 #include "hssk_internal.h"
+#include "hssk_matern.h"
 
 namespace {
 
@@ -23,7 +24,9 @@ constexpr size_t PR_LDS_POINT = sizeof(double) * (2 * PR_T * (PR_DMAX + 1) + PR_
 constexpr size_t PR_LDS_WIDE = sizeof(double) * (PR_T * (PR_DC + 1) + 32 * PR_DC + 32);
 
 // prediction[c] = sum_r w[r] k(x_r, t_c)   (no lambda: train and test points are different sets)
-template <int MODE>
+// MAT: the Matern kernels (types 3 and 4) -- the Gauss distance loop with the finish of hssk_matern.h; an instantiation of its
+// own, so that the code of the other three kernels is what it was
+template <int MODE, bool MAT = false>
 __global__ __launch_bounds__(PR_T) void kernel_predict_kernel(hssk_kernel_spec ks, const double* __restrict__ w, size_t ldw,
                                                               const double* __restrict__ T, int m,
                                                               double* __restrict__ pred, size_t ldo) {
@@ -45,7 +48,14 @@ __global__ __launch_bounds__(PR_T) void kernel_predict_kernel(hssk_kernel_spec k
     const int rend = (int)min((long long)PR_T, ks.n - r0);
     for (int r = 0; r < rend; r++) {
       double v;
-      if (ks.type == 2) {
+      if (MAT) {
+        double acc = 0.;
+        for (int i = 0; i < d; i++) {
+          const double df = xr[r * (PR_DMAX + 1) + i] - xt[tid * (PR_DMAX + 1) + i];
+          acc += df * df;
+        }
+        v = hssk_matern_rt(ks.type, acc, hssk_matern_c(ks.type, ks.h), ks.h);
+      } else if (ks.type == 2) {
         double Kss[8], Kpp[9];
         for (int j = 0; j < ks.p; j++) Kss[j] = 0.;
         for (int i = 0; i < d; i++) {
@@ -96,7 +106,7 @@ __device__ inline void anova_newton<0>(const double (&)[8], double (&K)[9], int,
 // The same sum beyond PR_DMAX coordinates: whole points no longer fit the LDS, so a tile of RT training points meets the
 // workgroup's 64 test points in passes of PR_DC coordinates.  What a pair has accumulated -- the distance (Gauss, Laplace) or the
 // p power sums of its per-coordinate exponentials (ANOVA) -- carries across the passes in registers; RT is what the registers
-// hold (32 distances, 8 x 8 power sums).  Per pair the coordinates are met in order and the pairs of a test point in training
+// hold (32 distances, 8 x 8 power sums; the Matern kernels, TYPE 3 and 4, carry the Gauss distance).  Per pair the coordinates are met in order and the pairs of a test point in training
 // order, as in kernel_predict_kernel: the same arithmetic, the same error bound.  The test points' pass is staged again for
 // every training tile (one staged value per RT differences).
 template <int TYPE, int RT, int MODE>
@@ -142,7 +152,7 @@ __global__ __launch_bounds__(PR_T) void kernel_predict_wide_kernel(hssk_kernel_s
             for (int q = 0; q < NS; q++)
               if (q < P) { acc[r][q] += pw; pw *= tmp; }
           } else {
-            acc[r][0] += TYPE == 0 ? df * df : fabs(df);
+            acc[r][0] += TYPE == 1 ? fabs(df) : df * df;
           }
         }
       }
@@ -157,6 +167,8 @@ __global__ __launch_bounds__(PR_T) void kernel_predict_wide_kernel(hssk_kernel_s
 #pragma unroll
           for (int q = 0; q < 8; q++) S[q] = acc[r][q < NS ? q : 0];
           anova_newton<8>(S, Kpp, P, v);
+        } else if (TYPE == 3 || TYPE == 4) {
+          v = hssk_matern<TYPE == 3 ? 3 : 4, 0>(acc[r][0], hssk_matern_c(TYPE, ks.h), ks.h);
         } else {
           v = exp(acc[r][0] * (TYPE == 0 ? -1. / h2 : -1. / ks.h));
         }
@@ -169,7 +181,8 @@ __global__ __launch_bounds__(PR_T) void kernel_predict_wide_kernel(hssk_kernel_s
 }
 
 inline void check_spec(const hssk_kernel_spec& ks) {
-  if (ks.type < 0 || ks.type > 2) throw std::invalid_argument("hssk kernel: type must be 0 (Gauss), 1 (Laplace) or 2 (ANOVA)");
+  if (ks.type < 0 || ks.type > 4)
+    throw std::invalid_argument("hssk kernel: type must be 0 (Gauss), 1 (Laplace), 2 (ANOVA), 3 (Matern32) or 4 (Matern52)");
   if (ks.d <= 0 || ks.n < 0 || !ks.X) throw std::invalid_argument("hssk kernel: bad point set");
   if (ks.type == 2 && (ks.p < 1 || ks.p > 8 || ks.p > ks.d)) throw std::invalid_argument("hssk kernel: ANOVA degree must be in [1, min(8, d)]");
 }

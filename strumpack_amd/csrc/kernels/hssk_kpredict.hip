@@ -4,7 +4,7 @@
 // Grid: test tiles of 64 points x splits of the training set.  A workgroup is four waves that share the 64 test points; wave w
 // takes the training tiles 4 c + w (64 points each) of the chunks c of its split.  Every (training tile, test tile) pair goes one
 // of two routes, the same for the whole wave:
-//   * matrix cores (Gauss only): the base-2 exponent |x~|^2 + |t~|^2 - 2 x~.t~ of 32 x 32 pairs is the accumulator of
+//   * matrix cores (Gauss, Matern): the base-2 exponent |x~|^2 + |t~|^2 - 2 x~.t~ of 32 x 32 pairs is the accumulator of
 //     v_mfma_f32_32x32x2_f32 over K = d + 2 coordinates (x~ = s (x - mean), s^2 = log2(e) / (2 h^2); the two norms are extra
 //     coordinates; training points along M, test points along N = the lane).  Taken iff the worst relative error the norm
 //     expansion can cause in a term, 4 (d + 4) 2^-24 (max |x~|^2 + max |t~|^2), is at most HSSK_KPREDICT_TAU;
@@ -13,8 +13,14 @@
 // Either way a lane multiplies 16 kernel values by their weights, adds them in FP32 and adds that one number to an FP64 running
 // sum: no FP32 sum is longer than 16 terms.  The four waves' sums are added in wave order, the splits' sums by a second launch
 // in split order, rounded once to float.  The split count depends on (n, m) alone, so the order of every sum is fixed.
+//
+// The Matern kernels (types 3 and 4) take both routes with the points scaled by sqrt(2 nu) / h instead: the
+// accumulator of the matrix cores -- or, in the difference form, the FP32 distance times 2 nu / h^2 -- is u = s^2, and the value is
+// hssk_matern_f32(u) = polynomial(s) exp2(-s log2 e), s = sqrt(max(u, 0)).  The route rule and its threshold are the Gauss ones,
+// read on these scaled points: |dk/du| <= 1/2, so an error in u costs a term no more than it costs a Gauss term.
 #include "hssk_device.h"
 #include "hssk_internal.h"
+#include "hssk_matern.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -31,7 +37,7 @@ struct KpArgs {
   const float *X, *T, *Xa, *Ta, *wpad, *xmax, *tmax;
   long long n;
   int m, d, type, p, ldn, ldm, chunks, splits, force_diff;
-  float s2;   // Gauss / ANOVA: log2(e) / (2 h^2); Laplace: log2(e) / h
+  float s2;   // Gauss / ANOVA: log2(e) / (2 h^2); Laplace: log2(e) / h; Matern: 2 nu / h^2
   double* partial;
   long long* dstats;
 };
@@ -119,12 +125,12 @@ __device__ inline float kp_diff16(const KpArgs& a, const float* tl, const float*
 #pragma unroll
     for (int i = 0; i < 16; i++) {
       const float df = xb[(FULL ? i : min(i, top)) * d + j] - t;
-      acc[i] += TYPE == 0 ? df * df : fabsf(df);
+      acc[i] += TYPE == 1 ? fabsf(df) : df * df;
     }
   }
   float s16 = 0.f;
 #pragma unroll
-  for (int i = 0; i < 16; i++) s16 += wb[i] * exp2f(-(acc[i] * a.s2));
+  for (int i = 0; i < 16; i++) s16 += wb[i] * (TYPE >= 3 ? hssk_matern_f32<TYPE >= 3 ? TYPE : 3>(acc[i] * a.s2) : exp2f(-(acc[i] * a.s2)));
   return s16;
 }
 
@@ -170,8 +176,9 @@ __device__ inline double kp_diff_tile(const KpArgs& a, const float* tl, long lon
   return dd;
 }
 
-// KSM k-steps of two coordinates: 2 KSM >= d + 2 rows of Xa / Ta
-template <int KSM>
+// KSM k-steps of two coordinates: 2 KSM >= d + 2 rows of Xa / Ta.  MT: 0 for the three kernels of the reference (the type is
+// read from the arguments), 3 / 4 for the Matern kernels, which get instantiations of their own
+template <int KSM, int MT>
 __global__ __launch_bounds__(256) void kp_main_kernel(KpArgs a) {
   HSSK_DYN_SHARED(float, kp_lds);
   double* red = (double*)kp_lds;              // [KP_W * 64]: the waves' sums
@@ -187,8 +194,8 @@ __global__ __launch_bounds__(256) void kp_main_kernel(KpArgs a) {
 #pragma unroll
   for (int g = 0; g < 2; g++)
 #pragma unroll
-    for (int s = 0; s < KSM; s++) bq[g][s] = a.type == 0 ? a.Ta[(size_t)(2 * s + half) * a.ldm + c0 + 32 * g + l32] : 0.f;
-  const double tm = a.type == 0 ? (double)a.tmax[tt] : 0.;
+    for (int s = 0; s < KSM; s++) bq[g][s] = (MT || a.type == 0) ? a.Ta[(size_t)(2 * s + half) * a.ldm + c0 + 32 * g + l32] : 0.f;
+  const double tm = (MT || a.type == 0) ? (double)a.tmax[tt] : 0.;
   const double rule = 4. * (d + 4) * 5.9604644775390625e-8;   // 4 (d + 4) 2^-24
   const long long ch0 = (long long)sp * a.chunks / a.splits, ch1 = (long long)(sp + 1) * a.chunks / a.splits;
   double dm0 = 0., dm1 = 0., dd = 0.;
@@ -196,7 +203,7 @@ __global__ __launch_bounds__(256) void kp_main_kernel(KpArgs a) {
   for (long long ch = ch0; ch < ch1; ch++) {
     const long long r0 = (ch * KP_W + wv) * KP_T;
     if (r0 >= a.n) continue;   // (a tile of padding only)
-    const bool mf = a.type == 0 && !a.force_diff && rule * ((double)a.xmax[r0 / KP_T] + tm) <= HSSK_KPREDICT_TAU;
+    const bool mf = (MT || a.type == 0) && !a.force_diff && rule * ((double)a.xmax[r0 / KP_T] + tm) <= HSSK_KPREDICT_TAU;
     if (mf) {
       nmf++;
 #pragma unroll
@@ -218,8 +225,8 @@ __global__ __launch_bounds__(256) void kp_main_kernel(KpArgs a) {
           const hssk_f4 wq = *(const hssk_f4*)(a.wpad + rb + 8 * q + 4 * half);
 #pragma unroll
           for (int i = 0; i < 4; i++) {
-            s0 += wq[i] * exp2f(-fmaxf(acc0[4 * q + i], 0.f));
-            s1 += wq[i] * exp2f(-fmaxf(acc1[4 * q + i], 0.f));
+            s0 += wq[i] * (MT ? hssk_matern_f32<MT ? MT : 3>(acc0[4 * q + i]) : exp2f(-fmaxf(acc0[4 * q + i], 0.f)));
+            s1 += wq[i] * (MT ? hssk_matern_f32<MT ? MT : 3>(acc1[4 * q + i]) : exp2f(-fmaxf(acc1[4 * q + i], 0.f)));
           }
         }
         dm0 += (double)s0;
@@ -227,7 +234,8 @@ __global__ __launch_bounds__(256) void kp_main_kernel(KpArgs a) {
       }
     } else {
       ndf++;
-      dd += a.type == 0 ? kp_diff_tile<0>(a, tl, r0, lane) : (a.type == 1 ? kp_diff_tile<1>(a, tl, r0, lane) : kp_diff_tile<2>(a, tl, r0, lane));
+      if (MT) dd += kp_diff_tile<MT>(a, tl, r0, lane);
+      else dd += a.type == 0 ? kp_diff_tile<0>(a, tl, r0, lane) : (a.type == 1 ? kp_diff_tile<1>(a, tl, r0, lane) : kp_diff_tile<2>(a, tl, r0, lane));
     }
   }
   // the two lane halves of a matrix-core column, then the routes: lane l = test point l = column l32 of group half
@@ -309,7 +317,7 @@ __global__ __launch_bounds__(256) void kp_wide_kernel(KpArgs a) {
                 for (int q = 0; q < NS; q++)
                   if (q < a.p) { acc[i][q] += pw; pw *= tmp; }
               } else {
-                acc[i][0] += TYPE == 0 ? df * df : fabsf(df);
+                acc[i][0] += TYPE == 1 ? fabsf(df) : df * df;
               }
             }
           }
@@ -328,6 +336,8 @@ __global__ __launch_bounds__(256) void kp_wide_kernel(KpArgs a) {
 #pragma unroll
               for (int q = 0; q < 8; q++) S[q] = acc[16 * g + i][q < NS ? q : 0];
               kp_newton<8>(S, Kpp, a.p, v);
+            } else if (TYPE >= 3) {
+              v = hssk_matern_f32<TYPE >= 3 ? TYPE : 3>(acc[16 * g + i][0] * a.s2);
             } else {
               v = exp2f(-(acc[16 * g + i][0] * a.s2));
             }
@@ -358,10 +368,25 @@ __global__ __launch_bounds__(256) void kp_zero_kernel(float* __restrict__ pred, 
   if (c < m) pred[c] = 0.f;
 }
 
+template <int KSM, int MT>
+void kp_launch_main_t(hssk_ctx* ctx, const KpArgs& a, int nt, size_t shm) {
+  hssk_rt::allow_dynamic_lds(kp_main_kernel<KSM, MT>, shm);
+  HSSK_LAUNCH((kp_main_kernel<KSM, MT>), dim3((unsigned)nt, (unsigned)a.splits), dim3(256), shm, ctx->stream, a);
+}
 template <int KSM>
 void kp_launch_main(hssk_ctx* ctx, const KpArgs& a, int nt, size_t shm) {
-  hssk_rt::allow_dynamic_lds(kp_main_kernel<KSM>, shm);
-  HSSK_LAUNCH((kp_main_kernel<KSM>), dim3((unsigned)nt, (unsigned)a.splits), dim3(256), shm, ctx->stream, a);
+  if (a.type == 3) kp_launch_main_t<KSM, 3>(ctx, a, nt, shm);
+  else if (a.type == 4) kp_launch_main_t<KSM, 4>(ctx, a, nt, shm);
+  else kp_launch_main_t<KSM, 0>(ctx, a, nt, shm);
+}
+
+// what the difference form multiplies a pair's FP32 distance by, and the scale of the prepared points of the matrix-core route
+inline float kp_s2(int type, double h) {
+  const double l2e = 1.4426950408889634;
+  return (float)(type >= 3 ? hssk_matern_c(type, h) : (type == 1 ? l2e / h : l2e / (2. * h * h)));
+}
+inline double kp_point_scale(int type, double h) {
+  return type >= 3 ? std::sqrt(type == 3 ? 3. : 5.) / h : std::sqrt(1.4426950408889634) / (h * std::sqrt(2.));
 }
 
 size_t kp_align(size_t v) { return (v + 255) & ~size_t(255); }
@@ -375,17 +400,23 @@ extern "C" int hssk_kernel_predict_splits(long long n, int m) {
   return (int)std::max<long long>(1, std::min(want, chunks));
 }
 
-extern "C" int hssk_kernel_predict_f32(hssk_ctx* ctx, const float* X, long long n, int d, int type, int p, double h, const float* w,
-                                       const float* T, int m, float* pred, long long* stats) {
+namespace {
+// The two public forms of each prediction.  hssk_kernel_predict_f32 / _wide take the three kernels of the reference and go on
+// refusing every other type code, as they always have; hssk_matern_predict_f32 / _wide take twice_nu = 3 or 5 and pass the type
+// 3 or 4 (`matern`).  `who` names the entry point in the messages.
+int kp_predict(const char* who_, bool matern, hssk_ctx* ctx, const float* X, long long n, int d, int type, int p, double h, const float* w,
+               const float* T, int m, float* pred, long long* stats) {
   HSSK_API_BEGIN
-  if (!ctx) throw std::invalid_argument("hssk_kernel_predict_f32: no context");
-  if (type < 0 || type > 2) throw std::invalid_argument("hssk_kernel_predict_f32: type must be 0 (Gauss), 1 (Laplace) or 2 (ANOVA)");
-  if (d < 1 || d > KP_DMAX) throw std::invalid_argument("hssk_kernel_predict_f32: point dimension must be in [1, 64]");
-  if (type == 2 && (p < 1 || p > 8 || p > d)) throw std::invalid_argument("hssk_kernel_predict_f32: ANOVA degree must be in [1, min(8, d)]");
-  if (n < 0 || n > (1LL << 31) - 1024) throw std::invalid_argument("hssk_kernel_predict_f32: training point count out of range");
-  if (m < 0 || m > (1 << 30)) throw std::invalid_argument("hssk_kernel_predict_f32: test point count out of range");
-  if (!(h > 0.)) throw std::invalid_argument("hssk_kernel_predict_f32: the kernel width must be positive");
-  if ((n > 0 && (!X || !w)) || (m > 0 && (!T || !pred))) throw std::invalid_argument("hssk_kernel_predict_f32: null pointer");
+  const std::string who(who_);
+  if (!ctx) throw std::invalid_argument(who + ": no context");
+  if (matern ? (type != 3 && type != 4) : (type < 0 || type > 2))
+    throw std::invalid_argument(who + (matern ? ": twice_nu must be 3 (Matern32) or 5 (Matern52)" : ": type must be 0 (Gauss), 1 (Laplace) or 2 (ANOVA)"));
+  if (d < 1 || d > KP_DMAX) throw std::invalid_argument(who + ": point dimension must be in [1, 64]");
+  if (type == 2 && (p < 1 || p > 8 || p > d)) throw std::invalid_argument(who + ": ANOVA degree must be in [1, min(8, d)]");
+  if (n < 0 || n > (1LL << 31) - 1024) throw std::invalid_argument(who + ": training point count out of range");
+  if (m < 0 || m > (1 << 30)) throw std::invalid_argument(who + ": test point count out of range");
+  if (!(h > 0.)) throw std::invalid_argument(who + ": the kernel width must be positive");
+  if ((n > 0 && (!X || !w)) || (m > 0 && (!T || !pred))) throw std::invalid_argument(who + ": null pointer");
   if (stats) for (int i = 0; i < 6; i++) stats[i] = 0;
   if (m == 0) return 0;
   if (n == 0) {
@@ -397,7 +428,7 @@ extern "C" int hssk_kernel_predict_f32(hssk_ctx* ctx, const float* X, long long 
   const int chunks = (int)((n + KP_W * KP_T - 1) / (KP_W * KP_T)), nt = (m + KP_T - 1) / KP_T;
   const int splits = hssk_kernel_predict_splits(n, m), ldn = chunks * KP_W * KP_T, ldm = nt * KP_T, tx = ldn / KP_T;
   const size_t shm = sizeof(double) * KP_W * KP_T + sizeof(float) * KP_T * (size_t)d;
-  if (shm > hssk_rt::max_lds_per_workgroup()) HSSK_UNSUPPORTED("the test tile does not fit the LDS of this device");
+  if (shm > hssk_rt::max_lds_per_workgroup()) { hssk_set_error(who + ": the test tile does not fit the LDS of this device"); return 2; }
   // scratch: statistics | partial means | Xa | Ta | padded weights | tile norms | partial sums
   const size_t o_st = 0, o_pm = 256, o_xa = kp_align(o_pm + sizeof(double) * KP_G * d), o_ta = kp_align(o_xa + sizeof(float) * (size_t)KP * ldn);
   const size_t o_wp = kp_align(o_ta + sizeof(float) * (size_t)KP * ldm), o_xm = kp_align(o_wp + sizeof(float) * (size_t)ldn);
@@ -405,19 +436,18 @@ extern "C" int hssk_kernel_predict_f32(hssk_ctx* ctx, const float* X, long long 
   const size_t total = o_pa + sizeof(double) * (size_t)splits * ldm;
   char* base = (char*)ctx->scratch(total);
   static const bool force = [] { const char* e = std::getenv("HSSK_KPREDICT_FORCE_DIFF"); return e && e[0] == '1'; }();
-  const double l2e = 1.4426950408889634;
   KpArgs a;
   a.X = X; a.T = T; a.Xa = (float*)(base + o_xa); a.Ta = (float*)(base + o_ta); a.wpad = (float*)(base + o_wp);
   a.xmax = (float*)(base + o_xm); a.tmax = (float*)(base + o_tm);
   a.n = n; a.m = m; a.d = d; a.type = type; a.p = type == 2 ? p : 1; a.ldn = ldn; a.ldm = ldm; a.chunks = chunks; a.splits = splits;
   a.force_diff = force ? 1 : 0;
-  a.s2 = (float)(type == 1 ? l2e / h : l2e / (2. * h * h));
+  a.s2 = kp_s2(type, h);
   a.partial = (double*)(base + o_pa);
   a.dstats = (long long*)(base + o_st);
   hssk_rt::memset_async(a.dstats, 0, 16, ctx->stream);
   if (stats) hssk_watch_start(ctx, 4);
   HSSK_LAUNCH(kp_mean_kernel, dim3(KP_G), dim3(256), 0, ctx->stream, X, d, n, (double*)(base + o_pm));
-  HSSK_LAUNCH(kp_prep_kernel, dim3((unsigned)(tx + nt)), dim3(64), 0, ctx->stream, X, n, T, m, d, KP, std::sqrt(l2e) / (h * std::sqrt(2.)),
+  HSSK_LAUNCH(kp_prep_kernel, dim3((unsigned)(tx + nt)), dim3(64), 0, ctx->stream, X, n, T, m, d, KP, kp_point_scale(type, h),
               (const double*)(base + o_pm), w, (float*)(base + o_xa), ldn, (float*)(base + o_ta), ldm, (float*)(base + o_wp),
               (float*)(base + o_xm), (float*)(base + o_tm), tx);
   if (stats) { hssk_watch_stop(ctx, 4); hssk_watch_start(ctx, 6); }
@@ -443,17 +473,19 @@ extern "C" int hssk_kernel_predict_f32(hssk_ctx* ctx, const float* X, long long 
   HSSK_API_END
 }
 
-extern "C" int hssk_kernel_predict_f32_wide(hssk_ctx* ctx, const float* X, long long n, int d, int type, int p, double h, const float* w,
-                                            const float* T, int m, float* pred, long long* stats) {
+int kp_predict_wide(const char* who_, bool matern, hssk_ctx* ctx, const float* X, long long n, int d, int type, int p, double h,
+                    const float* w, const float* T, int m, float* pred, long long* stats) {
   HSSK_API_BEGIN
-  if (!ctx) throw std::invalid_argument("hssk_kernel_predict_f32_wide: no context");
-  if (type < 0 || type > 2) throw std::invalid_argument("hssk_kernel_predict_f32_wide: type must be 0 (Gauss), 1 (Laplace) or 2 (ANOVA)");
-  if (d <= KP_DMAX) throw std::invalid_argument("hssk_kernel_predict_f32_wide: point dimension must be above 64 (hssk_kernel_predict_f32 takes the others)");
-  if (type == 2 && (p < 1 || p > 8)) throw std::invalid_argument("hssk_kernel_predict_f32_wide: ANOVA degree must be in [1, 8]");
-  if (n < 0 || n > (1LL << 31) - 1024) throw std::invalid_argument("hssk_kernel_predict_f32_wide: training point count out of range");
-  if (m < 0 || m > (1 << 30)) throw std::invalid_argument("hssk_kernel_predict_f32_wide: test point count out of range");
-  if (!(h > 0.)) throw std::invalid_argument("hssk_kernel_predict_f32_wide: the kernel width must be positive");
-  if ((n > 0 && (!X || !w)) || (m > 0 && (!T || !pred))) throw std::invalid_argument("hssk_kernel_predict_f32_wide: null pointer");
+  const std::string who(who_);
+  if (!ctx) throw std::invalid_argument(who + ": no context");
+  if (matern ? (type != 3 && type != 4) : (type < 0 || type > 2))
+    throw std::invalid_argument(who + (matern ? ": twice_nu must be 3 (Matern32) or 5 (Matern52)" : ": type must be 0 (Gauss), 1 (Laplace) or 2 (ANOVA)"));
+  if (d <= KP_DMAX) throw std::invalid_argument(who + ": point dimension must be above 64 (hssk_kernel_predict_f32 takes the others)");
+  if (type == 2 && (p < 1 || p > 8)) throw std::invalid_argument(who + ": ANOVA degree must be in [1, 8]");
+  if (n < 0 || n > (1LL << 31) - 1024) throw std::invalid_argument(who + ": training point count out of range");
+  if (m < 0 || m > (1 << 30)) throw std::invalid_argument(who + ": test point count out of range");
+  if (!(h > 0.)) throw std::invalid_argument(who + ": the kernel width must be positive");
+  if ((n > 0 && (!X || !w)) || (m > 0 && (!T || !pred))) throw std::invalid_argument(who + ": null pointer");
   if (stats) for (int i = 0; i < 6; i++) stats[i] = 0;
   if (m == 0) return 0;
   if (n == 0) {
@@ -466,12 +498,11 @@ extern "C" int hssk_kernel_predict_f32_wide(hssk_ctx* ctx, const float* X, long 
   // scratch: statistics | padded weights | partial sums
   const size_t o_st = 0, o_wp = 256, o_pa = kp_align(o_wp + sizeof(float) * (size_t)ldn);
   char* base = (char*)ctx->scratch(o_pa + sizeof(double) * (size_t)splits * ldm);
-  const double l2e = 1.4426950408889634;
   KpArgs a;
   a.X = X; a.T = T; a.Xa = nullptr; a.Ta = nullptr; a.wpad = (float*)(base + o_wp); a.xmax = nullptr; a.tmax = nullptr;
   a.n = n; a.m = m; a.d = d; a.type = type; a.p = type == 2 ? p : 1; a.ldn = ldn; a.ldm = ldm; a.chunks = chunks; a.splits = splits;
   a.force_diff = 1;
-  a.s2 = (float)(type == 1 ? l2e / h : l2e / (2. * h * h));
+  a.s2 = kp_s2(type, h);
   a.partial = (double*)(base + o_pa);
   a.dstats = (long long*)(base + o_st);
   hssk_rt::memset_async(a.dstats, 0, 16, ctx->stream);
@@ -481,6 +512,8 @@ extern "C" int hssk_kernel_predict_f32_wide(hssk_ctx* ctx, const float* X, long 
   const dim3 grid((unsigned)nt, (unsigned)splits);
   if (type == 0) HSSK_LAUNCH((kp_wide_kernel<0, 32>), grid, dim3(256), 0, ctx->stream, a);
   else if (type == 1) HSSK_LAUNCH((kp_wide_kernel<1, 32>), grid, dim3(256), 0, ctx->stream, a);
+  else if (type == 3) HSSK_LAUNCH((kp_wide_kernel<3, 32>), grid, dim3(256), 0, ctx->stream, a);
+  else if (type == 4) HSSK_LAUNCH((kp_wide_kernel<4, 32>), grid, dim3(256), 0, ctx->stream, a);
   else HSSK_LAUNCH((kp_wide_kernel<2, 16>), grid, dim3(256), 0, ctx->stream, a);
   if (stats) { hssk_watch_stop(ctx, 6); hssk_watch_start(ctx, 4); }
   HSSK_LAUNCH(kp_reduce_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)a.partial, ldm, splits, m, pred);
@@ -497,4 +530,22 @@ extern "C" int hssk_kernel_predict_f32_wide(hssk_ctx* ctx, const float* X, long 
     stats[5] = (long long)std::llround(ms_rest * 1e3);
   }
   HSSK_API_END
+}
+}  // namespace
+
+extern "C" int hssk_kernel_predict_f32(hssk_ctx* ctx, const float* X, long long n, int d, int type, int p, double h, const float* w,
+                                       const float* T, int m, float* pred, long long* stats) {
+  return kp_predict("hssk_kernel_predict_f32", false, ctx, X, n, d, type, p, h, w, T, m, pred, stats);
+}
+extern "C" int hssk_kernel_predict_f32_wide(hssk_ctx* ctx, const float* X, long long n, int d, int type, int p, double h, const float* w,
+                                            const float* T, int m, float* pred, long long* stats) {
+  return kp_predict_wide("hssk_kernel_predict_f32_wide", false, ctx, X, n, d, type, p, h, w, T, m, pred, stats);
+}
+extern "C" int hssk_matern_predict_f32(hssk_ctx* ctx, const float* X, long long n, int d, int twice_nu, double h, const float* w,
+                                       const float* T, int m, float* pred, long long* stats) {
+  return kp_predict("hssk_matern_predict_f32", true, ctx, X, n, d, twice_nu == 3 ? 3 : (twice_nu == 5 ? 4 : -1), 1, h, w, T, m, pred, stats);
+}
+extern "C" int hssk_matern_predict_f32_wide(hssk_ctx* ctx, const float* X, long long n, int d, int twice_nu, double h, const float* w,
+                                            const float* T, int m, float* pred, long long* stats) {
+  return kp_predict_wide("hssk_matern_predict_f32_wide", true, ctx, X, n, d, twice_nu == 3 ? 3 : (twice_nu == 5 ? 4 : -1), 1, h, w, T, m, pred, stats);
 }

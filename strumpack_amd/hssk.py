@@ -170,6 +170,7 @@ HSSK_SYMBOLS = [
     "hssk_cluster_median", "hssk_pchol_id_vbatched", "hssk_pchol_id_max_m", "hssk_pchol_id_rank_cap", "hssk_sum_partials", "hssk_gram_vbatched", "hssk_gram_gen_vbatched", "hssk_gram_gen_supported",
     "hssk_sgemm_sketch", "hssk_narrow_f32", "hssk_gather_elems_f32",
     "hssk_kernel_predict_f32", "hssk_kernel_predict_f32_wide", "hssk_kernel_predict_splits",
+    "hssk_matern_predict_f32", "hssk_matern_predict_f32_wide",
     "hssk_logabsdet_vbatched", "hssk_kernel_cross", "hssk_kernel_predict_cols",
     "hssk_kernel_matmul", "hssk_kernel_matmul_splits", "hssk_coldots",
     "hssk_krylov_start", "hssk_krylov_orth", "hssk_krylov_combine",
@@ -292,6 +293,9 @@ class Hssk:
         for fn in ("hssk_kernel_predict_f32", "hssk_kernel_predict_f32_wide"):     # (the second: d >= 65)
             getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_double,
                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        for fn in ("hssk_matern_predict_f32", "hssk_matern_predict_f32_wide"):     # (twice_nu in place of type and degree)
+            getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_double,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.hssk_kernel_predict_splits.argtypes = [C.c_longlong, C.c_int]
         L.hssk_logabsdet_vbatched.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.hssk_kernel_cross.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
@@ -366,8 +370,12 @@ class Hssk:
         (n, d), m = X.shape, T.shape[0]
         dX, dT, dw, dp = (self.array(X.ravel()), self.array(T.ravel()), self.array(w), self.empty((m,), np.float32))
         st = np.zeros(6, dtype=np.int64)
-        fn = self.lib.hssk_kernel_predict_f32 if d <= 64 else self.lib.hssk_kernel_predict_f32_wide
-        self.check(fn(self.ctx, dX.ptr, n, d, ktype, p, h, dw.ptr, dT.ptr, m, dp.ptr, st.ctypes.data if stats else None))
+        if ktype >= 3:     # the Matern kernels: entry points of their own, twice_nu = 3 / 5 for the types 3 / 4
+            fn = self.lib.hssk_matern_predict_f32 if d <= 64 else self.lib.hssk_matern_predict_f32_wide
+            self.check(fn(self.ctx, dX.ptr, n, d, 2 * ktype - 3, h, dw.ptr, dT.ptr, m, dp.ptr, st.ctypes.data if stats else None))
+        else:
+            fn = self.lib.hssk_kernel_predict_f32 if d <= 64 else self.lib.hssk_kernel_predict_f32_wide
+            self.check(fn(self.ctx, dX.ptr, n, d, ktype, p, h, dw.ptr, dT.ptr, m, dp.ptr, st.ctypes.data if stats else None))
         out = dp.get()
         for a in (dX, dT, dw, dp):
             a.free()
