@@ -299,6 +299,11 @@ void* SPX_d_struct_hssk_ctx(const CSPStructMat S);
  * those found a rank above the launch's speculated bound and redid the inner levels one by one. */
 long long SPX_tree_pass_launches(void);
 long long SPX_tree_pass_fallbacks(void);
+/* Diagnostics (process-wide counters) of the row IDs of the compression, over all levels and rounds.  out[0]: panels given to the
+ * Gram ID (hssk_pchol_id_vbatched); out[1]: those of them whose rank outgrew its rows and that the Householder ID redid; out[2]:
+ * panels that went to the Householder ID at once; out[3]: sum of the panels' sample rows d (for a kernel matrix: the sizes of
+ * the nodes' column sets); out[4]: sum of (node index + 1) d, which tells two assignments of the same sizes apart. */
+void SPX_id_route_counts(long long* out);
 /* The library keeps released device chunks in a process-wide cache for reuse (no hipMalloc / hipFree page-table work in solver
  * loops); the cache is invisible to the other allocators of the process (torch, RCCL).  Default cap: a fifth of the device's memory
  * (environment STRUMPACK_AMD_POOL_GB overrides).  _trim returns everything cached to the device now; _set_limit_gb changes the cap

@@ -38,7 +38,7 @@ SP_SYMBOLS = [
     "SPX_d_blr_front_factor", "SPX_d_blr_front_factor_device", "SPX_d_blr_front_time_phases", "SPX_blr_low_rank_algorithm", "SPX_d_blr_front_forward",
     "SPX_d_blr_front_backward", "SPX_d_blr_front_schur", "SPX_d_blr_front_schur_device", "SPX_d_blr_front_tile_ranks",
     "SPX_d_blr_front_stats", "SPX_d_blr_front_destroy",
-    "SPX_tree_pass_launches", "SPX_tree_pass_fallbacks",
+    "SPX_tree_pass_launches", "SPX_tree_pass_fallbacks", "SPX_id_route_counts",
     "SPX_device_pool_cached_bytes", "SPX_device_pool_limit_bytes", "SPX_device_pool_trim", "SPX_device_pool_set_limit_gb",
     "SPX_s_struct_from_dense_device", "SPX_s_struct_sketch_route", "SPX_s_struct_stats",
 ]
@@ -118,6 +118,8 @@ def load(path):
     for f in ("SPX_tree_pass_launches", "SPX_tree_pass_fallbacks", "SPX_device_pool_cached_bytes", "SPX_device_pool_limit_bytes"):
         getattr(L, f).argtypes = []
         getattr(L, f).restype = C.c_longlong
+    L.SPX_id_route_counts.argtypes = [vp]
+    L.SPX_id_route_counts.restype = None
     L.SPX_device_pool_trim.argtypes = []
     L.SPX_device_pool_trim.restype = None
     L.SPX_device_pool_set_limit_gb.argtypes = [C.c_double]

@@ -637,12 +637,18 @@ void DeviceHSS::tsqr_reduce(const std::vector<int>& ids, const std::vector<int>&
 
 // Row ID of the listed (node, basis) pairs from prepared panels W_k = S_k^T (ds[k] x m_k, contiguous, in tmp_):
 // truncated QRCP + X = R11^{-1} R12 on the device, then the commit of rank, permutation, skeleton indices.
+static std::atomic<long long> g_id_gram{0}, g_id_gram_redone{0}, g_id_householder{0}, g_id_rows{0}, g_id_rows_weighted{0};
+void id_route_counts(long long* out5) {
+  out5[0] = g_id_gram; out5[1] = g_id_gram_redone; out5[2] = g_id_householder; out5[3] = g_id_rows; out5[4] = g_id_rows_weighted;
+}
+
 void DeviceHSS::id_panels(const std::vector<int>& ids, const std::vector<int>& which, const std::vector<double*>& Ws_in,
                           const std::vector<int>& ds_in, const std::vector<const double*>* srcs, int ldsrc) {
   Arena& tmp = *tmp_;
   const size_t cnt = ids.size();
   std::vector<double*> Ws(Ws_in);
   std::vector<int> ds(ds_in);
+  for (size_t k = 0; k < cnt; k++) { g_id_rows += ds_in[k]; g_id_rows_weighted += (long long)(ids[k] + 1) * ds_in[k]; }
   if (srcs) {
     // panels that take the TSQR pre-reduction (more than 256 sample rows) are reduced in place: those need their copy
     std::vector<hssk_colgather_desc> cp;
@@ -754,6 +760,8 @@ void DeviceHSS::id_panels(const std::vector<int>& ids, const std::vector<int>& w
     id_dmax = std::max(id_dmax, ds[k]);
     id_mmax = std::max(id_mmax, m);
   }
+  g_id_householder += (long long)idd.size();
+  g_id_gram += (long long)pcd.size();
   if (!idd.empty()) ck(hssk_id_vbatched(ctx_, idd.data(), (int)idd.size()));
   for (size_t q = 0; q < pcd.size(); q++) { pcd[q].perm = perms[pck[q]]; pcd[q].rank = rank_block + pck[q]; }
   if (!pcd.empty()) ck(hssk_pchol_id_vbatched(ctx_, pcd.data(), (int)pcd.size()));
@@ -767,6 +775,7 @@ void DeviceHSS::id_panels(const std::vector<int>& ids, const std::vector<int>& w
     std::vector<size_t> rk_;
     for (size_t k = 0; k < cnt; k++)
       if (gram[k] && hall[k] < 0) { rid.push_back(ids[k]); rwh.push_back(which[k]); rW.push_back(Ws[k]); rds.push_back(ds[k]); rk_.push_back(k); }
+    g_id_gram_redone += (long long)rid.size();
     if (!rid.empty()) {
       if (gen) evaluate(rk_);
       tsqr_reduce(rid, rwh, rW, rds);

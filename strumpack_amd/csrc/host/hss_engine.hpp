@@ -86,6 +86,9 @@ class DeviceHSS;
 // it reported a rank above its bound -- process-wide counters, for the tests
 long long tree_pass_launches();
 long long tree_pass_fallbacks();
+// the routes DeviceHSS::id_panels took, process-wide, for the tests: panels given to the Gram ID, those of them redone by the
+// Householder ID, panels that went to the Householder ID at once, sum of the panels' sample rows d, sum of (node + 1) d
+void id_route_counts(long long* out5);
 
 struct PhaseStats {
   double t_compress = 0, t_sketch = 0, t_random = 0, t_tree = 0, t_factor = 0, t_solve = 0, t_mult = 0;

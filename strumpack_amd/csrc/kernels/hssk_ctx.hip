@@ -283,6 +283,7 @@ void hssk_ctx_destroy(hssk_ctx* c) {
       }
       c->recording = nullptr;
       c->require_mma = false;
+      c->knn_filtered = 0;   // (hssk_knn_filtered_count counts the calls on THIS context: a recycled one starts again)
       g_pool.push_back(c);
       return;
     }
