@@ -879,6 +879,20 @@ int hssk_logabsdet_vbatched(hssk_ctx* ctx, const hssk_logdet_desc* descs, int co
 int hssk_kernel_matmul(hssk_ctx* ctx, const hssk_kernel_spec* spec, int deriv, const double* B, long long ldb, int nc, double* out,
                        long long ldo, int splits);
 int hssk_kernel_matmul_splits(long long n);   /* what splits = 0 chooses: a function of n alone */
+/* out_j(i, c) = sum_r k(x_i, x_r) D_j(x_i, x_r) B(r, c) for the nj coordinates j = j0 .. j0 + nj - 1 in ONE pass over the pairs
+ * (one distance and one exponential per pair serve all of them): D_j = (x_j - y_j)^2 / h^2 (Gauss), |x_j - y_j| / h (Laplace),
+ * the derivative of k(x / l, y / l) in ln l_j at l = 1, so that sum_j k D_j = h dk/dh.  Block j is n x nc,
+ * column-major with leading dimension ldo, at out + (j - j0) out_stride; B as for hssk_kernel_matmul.  The diagonal and every
+ * pair of equal points give exactly 0; spec->lambda is not used.  The value of a coordinate does not depend on nj or on j0.
+ * Gauss and Laplace, d <= 64; 1 <= nj <= hssk_kernel_matmul_coord_max(), j0 + nj <= d.  Splits as for hssk_kernel_matmul
+ * (splits = 0: hssk_kernel_matmul_splits(n)), no atomics, bitwise repeatable.  Returns HSSK_UNSUPPORTED (2) for ANOVA and Matern,
+ * d > 64 and stage buffers above the device's LDS; 1 for nc outside 0 .. 64, j0 < 0, nj outside 1 .. max, j0 + nj > d, ldb or
+ * ldo below n, out_stride below one block (ldo (nc - 1) + n), null pointers and an output that overlaps B.  A refused call
+ * writes nothing.  n = 0 or nc = 0: nothing to do. */
+int hssk_kernel_matmul_coord(hssk_ctx* ctx, const hssk_kernel_spec* spec, int j0, int nj, const double* B, long long ldb, int nc,
+                             double* out, long long ldo, long long out_stride, int splits);
+int hssk_kernel_matmul_coord_max(void);     /* most coordinates of one launch */
+int hssk_kernel_matmul_coord_group(void);   /* the group size a caller with no preference takes (profiles/gp_ard.md) */
 /* ---- the same product in single precision per pair: the inner operator of the mixed-precision solves ----------
  * The promise of hssk_kernel_matmul_f32's matrix-core route: the worst error the norm expansion |x|^2 + |y|^2 - 2 x.y can add to
  * a base-2 exponent, 4 (d + 4) 2^-24 (max |x~|^2 of the row tile + max |x~|^2 of the training tile).  A pair of tiles above it is

@@ -86,6 +86,14 @@ int SPX_kernel_model_points(STRUMPACKKernel K, double* x);
  * doubles: quad_h = 1/2 alpha^T K' alpha, quad_lambda = 1/2 alpha^T alpha, trace_h, trace_lambda (the means), then the m values
  * s_k^T K' z_k and the m values s_k^T z_k.  Non-zero also for an ANOVA kernel and for m < 1. */
 int SPX_kernel_lml_gradient(STRUMPACKKernel K, int m, const double* Z, unsigned long long seed, double grad[2], double* terms);
+/* The same gradient with one length scale per coordinate (automatic relevance determination; Gauss and Laplace, d <= 64;
+ * DESIGN.md 8i): k_l(x, y) = k(x / l, y / l), theta_j = ln l_j taken at l = 1, i.e. on the points the model holds,
+ *   grad[j] = dL/dtheta_j = 1/2 alpha^T K_j alpha - 1/2 tr(H^-1 K_j),   K_j = K o D_j,   sum_j grad[j] = h dL/dh,
+ * D_j = (x_j - y_j)^2 / h^2 (Gauss), |x_j - y_j| / h (Laplace).  m, Z, seed as above.  grad: d doubles.  terms: NULL or
+ * 2 d + d m doubles: the d values 1/2 alpha^T K_j alpha, the d trace means, then per coordinate the m values s_k^T K_j z_k.
+ * A model fitted on X / w has dL/dw_j = grad[j] / w_j.  Non-zero, with the outputs untouched, without a kept model, for a float
+ * handle, an ANOVA or Matern kernel, d > 64 and m < 1. */
+int SPX_kernel_lml_gradient_coords(STRUMPACKKernel K, int m, const double* Z, unsigned long long seed, double* grad, double* terms);
 /* the n x m block of +-1 entries the seeded form uses: std::mt19937_64(seed), one bit per entry, column by column */
 int SPX_kernel_model_probes(STRUMPACKKernel K, int m, unsigned long long seed, double* Z);
 /* *out = ||y - (K + lambda I) alpha||_2 / ||y||_2 with the EXACT kernel matrix: how far the compressed fit is from the exact one */

@@ -248,6 +248,74 @@ LmlGradient Kernel<double>::log_marginal_likelihood_gradient(const DenseMatrix<d
   return g;
 }
 
+// ---- the same gradient per coordinate: one length scale each ---------------------------------------------------
+LmlGradientCoords Kernel<double>::log_marginal_likelihood_gradient_coords(int m, unsigned long long seed) const {
+  model("log_marginal_likelihood_gradient_coords");
+  if (m < 1) throw std::invalid_argument("log_marginal_likelihood_gradient_coords: at least one probe vector");
+  return log_marginal_likelihood_gradient_coords(model_probes(m, seed));
+}
+
+LmlGradientCoords Kernel<double>::log_marginal_likelihood_gradient_coords(const DenseMatrix<double>& Z) const {
+  const char* what = "log_marginal_likelihood_gradient_coords";
+  const Model& M = model(what);
+  if (device_type() != 0 && device_type() != 1) throw std::invalid_argument(std::string(what) + ": Gauss and Laplace kernels only");
+  if (d() > 64) throw std::invalid_argument(std::string(what) + ": at most 64 coordinates");
+  if (Z.cols() < 1) throw std::invalid_argument(std::string(what) + ": at least one probe vector");
+  if (Z.rows() != n()) throw std::invalid_argument(std::string(what) + ": one probe row per training point expected (cluster order)");
+  const int m = int(Z.cols()), dim = int(d()), CH = 64, group = std::min(dim, hssk_kernel_matmul_coord_group());
+  const long long nn = (long long)n();
+  const size_t blk = (size_t)nn * CH;
+  hssk_ctx* ctx = M.ctx();
+  grad_ms_[0] = grad_ms_[1] = grad_ms_[2] = 0.;
+  // B: alpha | the probes, S = H^-1 B, G_j = (K o D_j) B for one group of coordinates at a time; the dots of a block:
+  // [j CH, j CH + nc) S.G_j, [dim CH + j] alpha.G_j(:, 0).  Every buffer before any computation.
+  GradBuf bB(ctx, sizeof(double) * blk), bS(ctx, sizeof(double) * blk), bG(ctx, sizeof(double) * blk * group),
+      bD(ctx, sizeof(double) * (size_t)dim * (CH + 1));
+  double *dB = (double*)bB.p, *dS = (double*)bS.p, *dG = (double*)bG.p, *dD = (double*)bD.p;
+  const hssk_kernel_spec spec{M.dX, nn, dim, device_type(), degree(), width(), 0.};
+  LmlGradientCoords g;
+  g.m = m;
+  g.dtheta.assign(dim, 0.);
+  g.quad.assign(dim, 0.);
+  g.trace.assign(dim, 0.);
+  g.tc.assign((size_t)dim * m, 0.);
+  std::vector<double> dots((size_t)dim * (CH + 1), 0.);
+  for (int c0 = 0; c0 < m + 1; c0 += CH) {   // column c of alpha | Z
+    const int nc = std::min(CH, m + 1 - c0), lead = c0 == 0 ? 1 : 0, z0 = c0 == 0 ? 0 : c0 - 1, nz = nc - lead;
+    if (lead) ckk(hssk_memcpy_h2d(ctx, dB, M.weights.data(), (long long)sizeof(double) * nn));
+    if (nz > 0) ckk(hssk_memcpy2d_h2d(ctx, dB + (size_t)lead * nn, sizeof(double) * nn, Z.ptr(0, z0), sizeof(double) * Z.ld(), sizeof(double) * nn, nz));
+    ckk(hssk_memcpy_d2d(ctx, dS, dB, (long long)sizeof(double) * nn * nc));
+    hssk_watch_start(ctx, 2);
+    M.H.solve_device(nc, dS, nn);   // (once per block, the same buffer for every block: the recorded sweep is replayed)
+    hssk_watch_stop(ctx, 2);
+    for (int j0 = 0; j0 < dim; j0 += group) {
+      const int nj = std::min(group, dim - j0);
+      hssk_watch_start(ctx, 1);
+      ckk(hssk_kernel_matmul_coord(ctx, &spec, j0, nj, dB, nn, nc, dG, nn, (long long)blk, 0));
+      hssk_watch_stop(ctx, 1);
+      hssk_watch_start(ctx, 3);
+      for (int jj = 0; jj < nj; jj++) {
+        ckk(hssk_coldots(ctx, dS, nn, dG + jj * blk, nn, nn, nc, dD + (size_t)(j0 + jj) * CH));
+        if (lead) ckk(hssk_coldots(ctx, dB, nn, dG + jj * blk, nn, nn, 1, dD + (size_t)dim * CH + j0 + jj));
+      }
+      hssk_watch_stop(ctx, 3);
+    }
+    ckk(hssk_memcpy_d2h(ctx, dots.data(), dD, (long long)sizeof(double) * dim * (CH + 1)));
+    for (int j = 0; j < dim; j++) {
+      for (int c = lead; c < nc; c++) g.tc[(size_t)j * m + z0 + c - lead] = dots[(size_t)j * CH + c];
+      if (lead) g.quad[j] = 0.5 * dots[(size_t)dim * CH + j];
+    }
+  }
+  for (int w = 0; w < 3; w++) grad_ms_[w] = hssk_watch_read_ms(ctx, w + 1, nullptr);
+  for (int j = 0; j < dim; j++) {
+    long double s = 0.L;
+    for (int k = 0; k < m; k++) s += (long double)g.tc[(size_t)j * m + k];
+    g.trace[j] = (double)(s / m);
+    g.dtheta[j] = g.quad[j] - 0.5 * g.trace[j];
+  }
+  return g;
+}
+
 double Kernel<double>::model_residual() const {
   const Model& M = model("model_residual");
   if (device_type() != 0 && device_type() != 1) throw std::invalid_argument("model_residual: Gauss and Laplace kernels only");
@@ -1048,6 +1116,22 @@ int SPX_kernel_lml_gradient(STRUMPACKKernel K, int m, const double* Z, unsigned 
       terms[0] = g.quad_h; terms[1] = g.quad_lambda; terms[2] = g.trace_h; terms[3] = g.trace_lambda;
       std::copy(g.th.begin(), g.th.end(), terms + 4);
       std::copy(g.tl.begin(), g.tl.end(), terms + 4 + m);
+    }
+    return 0;
+  } catch (const std::exception& e) { report(e); return 1; }
+}
+int SPX_kernel_lml_gradient_coords(STRUMPACKKernel K, int m, const double* Z, unsigned long long seed, double* grad, double* terms) {
+  try {
+    auto k = model_of(K);
+    if (!k || m < 1 || !grad) return 1;
+    const kernel::LmlGradientCoords g = Z ? k->log_marginal_likelihood_gradient_coords(DenseMatrix<double>(k->n(), m, Z, k->n()))
+                                          : k->log_marginal_likelihood_gradient_coords(m, seed);
+    const std::size_t dim = k->d();
+    std::copy(g.dtheta.begin(), g.dtheta.end(), grad);
+    if (terms) {
+      std::copy(g.quad.begin(), g.quad.end(), terms);
+      std::copy(g.trace.begin(), g.trace.end(), terms + dim);
+      std::copy(g.tc.begin(), g.tc.end(), terms + 2 * dim);
     }
     return 0;
   } catch (const std::exception& e) { report(e); return 1; }

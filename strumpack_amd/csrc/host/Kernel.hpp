@@ -51,6 +51,14 @@ struct LmlGradient {
   std::vector<double> th, tl;                 // per probe: s_k^T (dK/dh z_k), s_k^T z_k
 };
 
+// what Kernel<double>::log_marginal_likelihood_gradient_coords returns: the gradient in theta_j = ln l_j, one length scale l_j per
+// coordinate, taken at l = 1
+struct LmlGradientCoords {
+  int m = 0;                                  // probes
+  std::vector<double> dtheta, quad, trace;    // per coordinate: dL/dtheta_j = quad_j - trace_j / 2, 1/2 alpha^T K_j alpha, mean_k tc[j][k]
+  std::vector<double> tc;                     // d x m, coordinate-major: tc[j m + k] = s_k^T (K_j z_k)
+};
+
 // what the solves with the EXACT kernel matrix report (Kernel<double>::model_refine / model_solve / predict_variance_exact)
 struct KrylovInfo {
   bool converged = true;                        // every column reached rtol
@@ -128,6 +136,15 @@ template <> class Kernel<double> {
   LmlGradient log_marginal_likelihood_gradient(const DenseM_t& Z) const;
   // the same with the Rademacher block model_probes(m, seed)
   LmlGradient log_marginal_likelihood_gradient(int m = 63, unsigned long long seed = 0) const;
+  // The gradient in one length scale per coordinate (automatic relevance determination; Gauss and Laplace, d <= 64).
+  // k_l(x, y) = k(x / l, y / l), theta_j = ln l_j at l = 1, i.e. on the points the model holds:
+  //   dL/dtheta_j = 1/2 alpha^T K_j alpha - 1/2 tr(H^-1 K_j),   K_j = K o D_j,  sum_j K_j = h dK/dh,
+  // K_j the EXACT matrices (hssk_kernel_matmul_coord: one pass over the pairs per group of coordinates), H^-1 the kept, compressed
+  // inverse as above, with the same bias at a loose tolerance.  Probes, blocks and alpha's place as in
+  // log_marginal_likelihood_gradient; one ULV solve per block serves all coordinates.  A caller who fitted on X / w has
+  // dL/dw_j = dtheta[j] / w_j.  gradient_ms() reports this call too.
+  LmlGradientCoords log_marginal_likelihood_gradient_coords(const DenseM_t& Z) const;
+  LmlGradientCoords log_marginal_likelihood_gradient_coords(int m = 63, unsigned long long seed = 0) const;
   // n x m entries +-1 from std::mt19937_64(seed), one bit per entry, column by column
   DenseM_t model_probes(int m, unsigned long long seed) const;
   // ||y - (K + lambda I) alpha||_2 / ||y||_2 with the EXACT kernel matrix (one product; the norms in long double)

@@ -39,16 +39,11 @@
 #include "hssk_device.h"
 #include "hssk_internal.h"
 #include "hssk_kpair.h"
+#include "hssk_kmatmul_tile.h"
 
 namespace {
 
-constexpr int KM_T = 256;      // threads: four waves
-constexpr int KM_R = 64;       // output rows per workgroup
-constexpr int KM_K = 16;       // training points per stage
-constexpr int KM_KP = KM_K + 1;
-constexpr int KM_DMAX = 64;    // most coordinates a whole point keeps in the LDS
-constexpr int KM_DC = 32;      // coordinates per pass beyond that
-constexpr long long KM_GRID = 512;   // workgroups hssk_kernel_matmul_splits aims at (two per compute unit of an MI355X)
+constexpr int KM_DC = 32;      // coordinates per pass beyond KM_DMAX
 
 // doubles of dynamic LDS: two stages of g | two stages of B | row points [64][dp] | training points 2 x [16][dp]
 inline size_t km_lds_doubles(int dp) { return 4 * (size_t)KM_R * KM_KP + (size_t)KM_R * dp + 2 * (size_t)KM_K * dp; }

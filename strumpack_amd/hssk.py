@@ -173,6 +173,7 @@ HSSK_SYMBOLS = [
     "hssk_matern_predict_f32", "hssk_matern_predict_f32_wide",
     "hssk_logabsdet_vbatched", "hssk_kernel_cross", "hssk_kernel_predict_cols",
     "hssk_kernel_matmul", "hssk_kernel_matmul_splits", "hssk_coldots",
+    "hssk_kernel_matmul_coord", "hssk_kernel_matmul_coord_max", "hssk_kernel_matmul_coord_group",
     "hssk_krylov_start", "hssk_krylov_orth", "hssk_krylov_combine",
     "hssk_kernel_matmul_f32", "hssk_kernel_matmul_f32_prep", "hssk_kernel_matmul_f32_prep_bytes", "hssk_kernel_matmul_f32_splits",
 ]
@@ -303,6 +304,11 @@ class Hssk:
         L.hssk_kernel_matmul.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong,
                                          C.c_int]
         L.hssk_kernel_matmul_splits.argtypes = [C.c_longlong]
+        # per-coordinate derivatives: j0, nj in front of B; the stride between the nj output blocks behind ldo
+        L.hssk_kernel_matmul_coord.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
+                                               C.c_longlong, C.c_longlong, C.c_int]
+        L.hssk_kernel_matmul_coord_max.argtypes = []
+        L.hssk_kernel_matmul_coord_group.argtypes = []
         # the FP32 inner product of the mixed-precision solves: prepared points, FP64 blocks; the last argument: 4 host long longs
         L.hssk_kernel_matmul_f32_prep_bytes.restype = C.c_longlong
         L.hssk_kernel_matmul_f32_prep_bytes.argtypes = [C.c_longlong, C.c_int]

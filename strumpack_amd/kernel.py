@@ -13,7 +13,7 @@ KERNEL_SYMBOLS = [
     "STRUMPACK_kernel_predict_float", "SPX_kernel_predict_device_float", "SPX_kernel_predict_stats",
     "SPX_kernel_keep_model", "SPX_kernel_logabsdet", "SPX_kernel_log_marginal_likelihood", "SPX_kernel_predict_variance_double",
     "SPX_kernel_variance_ms", "SPX_kernel_model_set_lambda", "SPX_kernel_model_write", "SPX_kernel_model_labels",
-    "SPX_kernel_model_points", "SPX_kernel_lml_gradient", "SPX_kernel_model_probes", "SPX_kernel_model_residual",
+    "SPX_kernel_model_points", "SPX_kernel_lml_gradient", "SPX_kernel_lml_gradient_coords", "SPX_kernel_model_probes", "SPX_kernel_model_residual",
     "SPX_kernel_gradient_ms", "SPX_kernel_model_refine", "SPX_kernel_model_solve", "SPX_kernel_predict_variance_exact_double",
     "SPX_kernel_krylov_ms", "SPX_kernel_set_krylov_inner", "SPX_kernel_krylov_inner", "SPX_kernel_krylov_stats",
 ]
@@ -54,6 +54,7 @@ def load(path):
     L.SPX_kernel_model_labels.argtypes = [vp, vp]
     L.SPX_kernel_model_points.argtypes = [vp, vp]
     L.SPX_kernel_lml_gradient.argtypes = [vp, C.c_int, vp, C.c_ulonglong, vp, vp]
+    L.SPX_kernel_lml_gradient_coords.argtypes = [vp, C.c_int, vp, C.c_ulonglong, vp, vp]
     L.SPX_kernel_model_probes.argtypes = [vp, C.c_int, C.c_ulonglong, vp]
     L.SPX_kernel_model_residual.argtypes = [vp, C.POINTER(C.c_double)]
     L.SPX_kernel_gradient_ms.argtypes = [vp, vp]
@@ -72,11 +73,28 @@ def load(path):
 class KernelRegression:
     """Kernel ridge regression classifier, same shape as the reference's STRUMPACKKernel (fit / predict)."""
 
-    def __init__(self, lib, h=1.0, lam=4.0, kernel="rbf", degree=1, argv=(), keep_model=False):
+    def __init__(self, lib, h=1.0, lam=4.0, kernel="rbf", degree=1, argv=(), keep_model=False, widths=None):
         """keep_model (double fits only): the fit keeps its factored matrix, so that logabsdet, log_marginal_likelihood,
-        predict_variance, set_lambda and write_model work afterwards"""
+        predict_variance, set_lambda and write_model work afterwards.  widths (None, or d positive values): one length scale per
+        coordinate (automatic relevance determination), k(x / widths, y / widths): fit divides the columns of X by them, and so
+        do decision_function, predict and predict_variance with their test points; the model then holds the scaled points.
+        None changes nothing anywhere."""
         self.L, self.h, self.lam, self.ktype, self.p, self.argv = lib, h, lam, KERNEL_TYPES[kernel], degree, list(argv)
         self.K, self.dtype, self.keep_model = None, np.dtype(np.float64), bool(keep_model)
+        self.widths = None
+        if widths is not None:
+            w = np.array(widths, dtype=np.float64)
+            if w.ndim != 1 or w.size < 1 or not np.all(np.isfinite(w)) or not np.all(w > 0.0):
+                raise ValueError("widths: a vector of positive, finite length scales, one per coordinate")
+            self.widths = w
+
+    def _scaled(self, P, what):
+        """the points P (rows) in the coordinates the model works in: divided by widths where those are set"""
+        if self.widths is None:
+            return P
+        if P.ndim != 2 or P.shape[1] != len(self.widths):
+            raise ValueError("%s: %d widths, but points with shape %s" % (what, len(self.widths), P.shape))
+        return P / self.widths.astype(P.dtype)
 
     def fit(self, X, y, neighbors=None):
         """float32 X: the float entry points (promoted fit, FP32 prediction; the fit works on a copy of X, kept in cluster
@@ -85,6 +103,7 @@ class KernelRegression:
         self.dtype = np.dtype(np.float32 if np.asarray(X).dtype == np.float32 else np.float64)
         sfx = "float" if self.dtype == np.float32 else "double"
         X = np.array(X, dtype=self.dtype, order="C")     # n x d row-major == d x n column-major
+        X = np.ascontiguousarray(self._scaled(X, "fit"))
         y = np.array(y, dtype=self.dtype, order="C")
         self.n, self.d = X.shape
         self.X_, self.y_ = X, y   # (the float entry points reorder both in place and keep pointing at X)
@@ -120,7 +139,7 @@ class KernelRegression:
         matrix is K + lam I only up to the compression tolerance, so a value may be slightly negative.  exact=True: the solve
         with the exact kernel matrix instead (see refine), up to rtol; info=True then also returns the dict of that solve;
         inner / inner_rtol: see refine"""
-        T = np.ascontiguousarray(T, dtype=np.float64)
+        T = np.ascontiguousarray(self._scaled(np.asarray(T, dtype=np.float64), "predict_variance"))
         out = np.zeros(T.shape[0])
         if not exact:
             if self.L.SPX_kernel_predict_variance_double(self.K, T.shape[0], T.ctypes.data, out.ctypes.data):
@@ -254,7 +273,7 @@ class KernelRegression:
         return y
 
     def model_points(self):
-        """the training points in cluster order (n x d)"""
+        """the training points in cluster order (n x d) as the model holds them: with widths set, the SCALED points X / widths"""
         X = np.zeros((self.n, self.d))
         if self.L.SPX_kernel_model_points(self.K, X.ctypes.data):
             raise RuntimeError("no kept model")
@@ -289,6 +308,31 @@ class KernelRegression:
         return float(grad[0]), float(grad[1]), dict(quad_h=t[0], quad_lambda=t[1], trace_h=t[2], trace_lambda=t[3],
                                                     th=t[4:4 + m].copy(), tl=t[4 + m:].copy())
 
+    def log_marginal_likelihood_gradient_coords(self, probes=63, seed=0, Z=None, terms=False):
+        """the gradient of the log marginal likelihood in one length scale per coordinate (Gauss and Laplace, d <= 64): a length-d
+        array.  With widths set: dL/dwidths_j of the kernel k(x / widths, y / widths).  Without: dL/dtheta_j, theta_j = ln l_j
+        at l = 1 (the same number as dL/dwidths at widths = 1); its sum over j is h dL/dh.  The exact matrices K o D_j against the
+        kept, compressed inverse; probes, seed and Z as in log_marginal_likelihood_gradient.  terms=True: also a dict with dtheta,
+        quad and trace (length d) and the per-probe values tc (d x m)."""
+        if Z is not None:
+            Z = np.asfortranarray(Z, dtype=np.float64)
+            if Z.ndim != 2 or Z.shape[0] != self.n or Z.shape[1] < 1:
+                raise ValueError("log_marginal_likelihood_gradient_coords: Z must be n x m with m >= 1")
+            m, zp = Z.shape[1], Z.ctypes.data
+        else:
+            m, zp = int(probes), None
+        if m < 1:
+            raise ValueError("log_marginal_likelihood_gradient_coords: at least one probe vector")
+        d = self.d
+        grad, t = np.zeros(d), np.zeros(2 * d + d * m)
+        if self.L.SPX_kernel_lml_gradient_coords(self.K, m, zp, int(seed), grad.ctypes.data, t.ctypes.data):
+            raise RuntimeError("SPX_kernel_lml_gradient_coords failed (a kept model of a Gauss or Laplace fit in at most 64 "
+                               "coordinates is needed)")
+        out = grad.copy() if self.widths is None else grad / self.widths
+        if not terms:
+            return out
+        return out, dict(dtheta=grad, quad=t[:d].copy(), trace=t[d:2 * d].copy(), tc=t[2 * d:].reshape(d, m).copy())
+
     def gradient_ms(self):
         out = np.zeros(3)
         if self.L.SPX_kernel_gradient_ms(self.K, out.ctypes.data):
@@ -309,12 +353,14 @@ class KernelRegression:
             import torch
             if T.dtype != torch.float32 or not T.is_contiguous() or T.dim() != 2 or T.shape[1] != self.d:
                 raise ValueError("decision_function: a contiguous float32 m x d tensor is expected")
+            if self.widths is not None:
+                T = (T / torch.as_tensor(self.widths, dtype=torch.float32, device=T.device)).contiguous()
             out = torch.empty(T.shape[0], dtype=torch.float32, device=T.device)
             torch.cuda.synchronize(T.device)
             if self.L.SPX_kernel_predict_device_float(self.K, T.shape[0], T.data_ptr(), out.data_ptr()):
                 raise RuntimeError("SPX_kernel_predict_device_float failed")
             return out
-        T = np.ascontiguousarray(T, dtype=self.dtype)
+        T = np.ascontiguousarray(self._scaled(np.asarray(T, dtype=self.dtype), "decision_function"))
         out = np.zeros(T.shape[0], dtype=self.dtype)
         sfx = "float" if self.dtype == np.float32 else "double"
         getattr(self.L, "STRUMPACK_kernel_predict_" + sfx)(self.K, T.shape[0], T.ctypes.data, out.ctypes.data)
