@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <stdexcept>
 #include <vector>
 
 #include "hssk.h"
@@ -79,6 +80,20 @@ class DevicePool {
   }
   size_t cached_ = 0, limit_ = 0;
   bool limit_set_ = false;
+};
+
+// a pool chunk (of at least 256 bytes) for the length of a scope; the context's stream has drained when the chunk goes back
+struct PoolBuf {
+  void* p = nullptr;
+  size_t bytes;
+  hssk_ctx* ctx;
+  PoolBuf(hssk_ctx* c, size_t b) : bytes(std::max<size_t>(b, 256)), ctx(c) {
+    p = DevicePool::get().acquire(bytes);
+    if (!p) throw std::runtime_error(hssk_last_error());
+  }
+  PoolBuf(const PoolBuf&) = delete;
+  PoolBuf& operator=(const PoolBuf&) = delete;
+  ~PoolBuf() { hssk_sync(ctx); DevicePool::get().release(p, bytes); }
 };
 
 namespace HSS { using strumpack::DevicePool; }

@@ -79,21 +79,13 @@ DenseMatrix<double> Kernel<double>::model_set_lambda(double lambda) {
   return w;
 }
 
-namespace {
-struct GradBuf {   // a device pool chunk for the length of a call
-  void* p = nullptr; size_t bytes; hssk_ctx* ctx;
-  GradBuf(hssk_ctx* c, size_t b) : bytes(std::max<size_t>(b, 256)), ctx(c) { p = DevicePool::get().acquire(bytes); if (!p) throw std::runtime_error(hssk_last_error()); }
-  ~GradBuf() { hssk_sync(ctx); DevicePool::get().release(p, bytes); }
-};
-}  // namespace
-
 // the device blocks of a Krylov call, for blocks of at most ncmax columns: restart + 1 basis blocks, Z (what the ULV solve works
 // on: always this buffer, so that its recorded sweep is replayed), W (the product; the residual's A x at the start of a cycle),
 // U (the update), B and X for callers that have none, and the small coefficient arrays
 struct Kernel<double>::KrylovWork {
   long long n;
   int ncmax, m;   // m: steps of a cycle = min(restart, maxit)
-  GradBuf bV, bZ, bW, bU, bB, bX, bS, bP;
+  PoolBuf bV, bZ, bW, bU, bB, bX, bS, bP;
   double *V, *Z, *W, *U, *B, *X, *Y, *Hout, *norms, *ones;
   void* prep = nullptr;   // mixed mode: the prepared float points of hssk_kernel_matmul_f32 (prep_bytes > 0)
   std::size_t prep_bytes;
@@ -137,12 +129,7 @@ std::vector<double> Kernel<double>::variance_chunks(const Model& M, const DenseM
   var_ms_[0] = var_ms_[1] = var_ms_[2] = 0.;
   if (m == 0) return var;
   hssk_ctx* ctx = M.ctx();
-  struct Buf {   // a device pool chunk for the length of the call
-    void* p = nullptr; size_t bytes; hssk_ctx* ctx;
-    Buf(hssk_ctx* c, size_t b) : bytes(std::max<size_t>(b, 256)), ctx(c) { p = DevicePool::get().acquire(bytes); if (!p) throw std::runtime_error(hssk_last_error()); }
-    ~Buf() { hssk_sync(ctx); DevicePool::get().release(p, bytes); }
-  };
-  Buf bT(ctx, sizeof(double) * dim * m), bK(ctx, sizeof(double) * nn * CH), bD(ctx, sizeof(double) * CH * CH), bP(ctx, sizeof(double) * m);
+  PoolBuf bT(ctx, sizeof(double) * dim * m), bK(ctx, sizeof(double) * nn * CH), bD(ctx, sizeof(double) * CH * CH), bP(ctx, sizeof(double) * m);
   double *dT = (double*)bT.p, *dK = (double*)bK.p, *dD = (double*)bD.p, *dP = (double*)bP.p;
   ckk(hssk_memcpy2d_h2d(ctx, dT, sizeof(double) * dim, test.data(), sizeof(double) * test.ld(), sizeof(double) * dim, m));
   std::vector<double> ktt(m, 0.), quad(m, 0.);
@@ -191,6 +178,26 @@ DenseMatrix<double> Kernel<double>::model_probes(int m, unsigned long long seed)
   return Z;
 }
 
+namespace {
+// Block c0 of alpha | Z for both gradients: nc columns, the first of them alpha iff lead, the others the probes from z0 on.  They
+// go to dB, their copy to dS, and S = H^-1 B is solved there (stopwatch 2) -- once per block, the same buffer for every block:
+// the recorded sweep is replayed.
+struct GradBlock { int nc, lead, z0; };
+template <class MODEL>
+GradBlock grad_block(const MODEL& M, const DenseMatrix<double>& Z, int c0, int CH, double* dB, double* dS) {
+  const long long nn = (long long)Z.rows();
+  hssk_ctx* ctx = M.ctx();
+  const int nc = std::min(CH, int(Z.cols()) + 1 - c0), lead = c0 == 0 ? 1 : 0, z0 = c0 == 0 ? 0 : c0 - 1, nz = nc - lead;
+  if (lead) ckk(hssk_memcpy_h2d(ctx, dB, M.weights.data(), (long long)sizeof(double) * nn));
+  if (nz > 0) ckk(hssk_memcpy2d_h2d(ctx, dB + (size_t)lead * nn, sizeof(double) * nn, Z.ptr(0, z0), sizeof(double) * Z.ld(), sizeof(double) * nn, nz));
+  ckk(hssk_memcpy_d2d(ctx, dS, dB, (long long)sizeof(double) * nn * nc));
+  hssk_watch_start(ctx, 2);
+  M.H.solve_device(nc, dS, nn);
+  hssk_watch_stop(ctx, 2);
+  return {nc, lead, z0};
+}
+}  // namespace
+
 LmlGradient Kernel<double>::log_marginal_likelihood_gradient(int m, unsigned long long seed) const {
   model("log_marginal_likelihood_gradient");
   if (m < 1) throw std::invalid_argument("log_marginal_likelihood_gradient: at least one probe vector");
@@ -207,7 +214,7 @@ LmlGradient Kernel<double>::log_marginal_likelihood_gradient(const DenseMatrix<d
   hssk_ctx* ctx = M.ctx();
   grad_ms_[0] = grad_ms_[1] = grad_ms_[2] = 0.;
   // B: alpha | the probes, S = H^-1 B, G = K' B; the dots of a block: [0, 64) S.G, [64, 128) S.B, [128] alpha.G(:, 0)
-  GradBuf bB(ctx, sizeof(double) * nn * CH), bS(ctx, sizeof(double) * nn * CH), bG(ctx, sizeof(double) * nn * CH), bD(ctx, sizeof(double) * (2 * CH + 1));
+  PoolBuf bB(ctx, sizeof(double) * nn * CH), bS(ctx, sizeof(double) * nn * CH), bG(ctx, sizeof(double) * nn * CH), bD(ctx, sizeof(double) * (2 * CH + 1));
   double *dB = (double*)bB.p, *dS = (double*)bS.p, *dG = (double*)bG.p, *dD = (double*)bD.p;
   const hssk_kernel_spec spec{M.dX, nn, dim, device_type(), degree(), width(), 0.};
   LmlGradient g;
@@ -216,13 +223,8 @@ LmlGradient Kernel<double>::log_marginal_likelihood_gradient(const DenseMatrix<d
   std::vector<double> dots(2 * CH + 1, 0.);
   double aga = 0.;
   for (int c0 = 0; c0 < m + 1; c0 += CH) {   // column c of alpha | Z
-    const int nc = std::min(CH, m + 1 - c0), lead = c0 == 0 ? 1 : 0, z0 = c0 == 0 ? 0 : c0 - 1, nz = nc - lead;
-    if (lead) ckk(hssk_memcpy_h2d(ctx, dB, M.weights.data(), (long long)sizeof(double) * nn));
-    if (nz > 0) ckk(hssk_memcpy2d_h2d(ctx, dB + (size_t)lead * nn, sizeof(double) * nn, Z.ptr(0, z0), sizeof(double) * Z.ld(), sizeof(double) * nn, nz));
-    ckk(hssk_memcpy_d2d(ctx, dS, dB, (long long)sizeof(double) * nn * nc));
-    hssk_watch_start(ctx, 2);
-    M.H.solve_device(nc, dS, nn);   // (the same buffer for every block: the recorded sweep is replayed)
-    hssk_watch_stop(ctx, 2);
+    const GradBlock b = grad_block(M, Z, c0, CH, dB, dS);
+    const int nc = b.nc, lead = b.lead, z0 = b.z0;
     hssk_watch_start(ctx, 1);
     ckk(hssk_kernel_matmul(ctx, &spec, 1, dB, nn, nc, dG, nn, 0));
     hssk_watch_stop(ctx, 1);
@@ -269,7 +271,7 @@ LmlGradientCoords Kernel<double>::log_marginal_likelihood_gradient_coords(const 
   grad_ms_[0] = grad_ms_[1] = grad_ms_[2] = 0.;
   // B: alpha | the probes, S = H^-1 B, G_j = (K o D_j) B for one group of coordinates at a time; the dots of a block:
   // [j CH, j CH + nc) S.G_j, [dim CH + j] alpha.G_j(:, 0).  Every buffer before any computation.
-  GradBuf bB(ctx, sizeof(double) * blk), bS(ctx, sizeof(double) * blk), bG(ctx, sizeof(double) * blk * group),
+  PoolBuf bB(ctx, sizeof(double) * blk), bS(ctx, sizeof(double) * blk), bG(ctx, sizeof(double) * blk * group),
       bD(ctx, sizeof(double) * (size_t)dim * (CH + 1));
   double *dB = (double*)bB.p, *dS = (double*)bS.p, *dG = (double*)bG.p, *dD = (double*)bD.p;
   const hssk_kernel_spec spec{M.dX, nn, dim, device_type(), degree(), width(), 0.};
@@ -281,13 +283,8 @@ LmlGradientCoords Kernel<double>::log_marginal_likelihood_gradient_coords(const 
   g.tc.assign((size_t)dim * m, 0.);
   std::vector<double> dots((size_t)dim * (CH + 1), 0.);
   for (int c0 = 0; c0 < m + 1; c0 += CH) {   // column c of alpha | Z
-    const int nc = std::min(CH, m + 1 - c0), lead = c0 == 0 ? 1 : 0, z0 = c0 == 0 ? 0 : c0 - 1, nz = nc - lead;
-    if (lead) ckk(hssk_memcpy_h2d(ctx, dB, M.weights.data(), (long long)sizeof(double) * nn));
-    if (nz > 0) ckk(hssk_memcpy2d_h2d(ctx, dB + (size_t)lead * nn, sizeof(double) * nn, Z.ptr(0, z0), sizeof(double) * Z.ld(), sizeof(double) * nn, nz));
-    ckk(hssk_memcpy_d2d(ctx, dS, dB, (long long)sizeof(double) * nn * nc));
-    hssk_watch_start(ctx, 2);
-    M.H.solve_device(nc, dS, nn);   // (once per block, the same buffer for every block: the recorded sweep is replayed)
-    hssk_watch_stop(ctx, 2);
+    const GradBlock b = grad_block(M, Z, c0, CH, dB, dS);
+    const int nc = b.nc, lead = b.lead, z0 = b.z0;
     for (int j0 = 0; j0 < dim; j0 += group) {
       const int nj = std::min(group, dim - j0);
       hssk_watch_start(ctx, 1);
@@ -321,7 +318,7 @@ double Kernel<double>::model_residual() const {
   if (device_type() != 0 && device_type() != 1) throw std::invalid_argument("model_residual: Gauss and Laplace kernels only");
   const long long nn = (long long)n();
   hssk_ctx* ctx = M.ctx();
-  GradBuf bB(ctx, sizeof(double) * nn), bG(ctx, sizeof(double) * nn);
+  PoolBuf bB(ctx, sizeof(double) * nn), bG(ctx, sizeof(double) * nn);
   const hssk_kernel_spec spec{M.dX, nn, int(d()), device_type(), degree(), width(), lambda_};
   ckk(hssk_memcpy_h2d(ctx, bB.p, M.weights.data(), (long long)sizeof(double) * nn));
   ckk(hssk_kernel_matmul(ctx, &spec, 0, (const double*)bB.p, nn, 1, (double*)bG.p, nn, 0));
@@ -676,16 +673,6 @@ struct Kernel<float>::Resident {
 };
 
 namespace {
-struct PoolBuf {   // a device pool chunk for the length of a call
-  void* p = nullptr;
-  size_t bytes = 0;
-  hssk_ctx* ctx;
-  PoolBuf(hssk_ctx* c, size_t b) : bytes(std::max<size_t>(b, 256)), ctx(c) {
-    p = DevicePool::get().acquire(bytes);
-    if (!p) throw std::runtime_error(hssk_last_error());
-  }
-  ~PoolBuf() { hssk_sync(ctx); DevicePool::get().release(p, bytes); }
-};
 // a user-defined float kernel function in front of the FP64 front end (its points are exactly the widened floats)
 class PromotedUserKernel : public Kernel<double> {
  public:

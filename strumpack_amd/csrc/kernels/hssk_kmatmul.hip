@@ -39,6 +39,7 @@
 #include "hssk_device.h"
 #include "hssk_internal.h"
 #include "hssk_kpair.h"
+#include "hssk_kmatmul_split.h"
 #include "hssk_kmatmul_tile.h"
 
 namespace {
@@ -207,6 +208,27 @@ void km_launch(hssk_ctx* ctx, const hssk_kernel_spec& ks, const double* B, size_
   HSSK_LAUNCH((kmatmul_kernel<TYPE, DERIV, WIDE>), grid, dim3(KM_T), shm, ctx->stream, ks, B, ldb, nc, out, ldo, slab, per);
 }
 
+// type -> deriv -> wide: the 16 instances
+template <int TYPE, int DERIV, class... A>
+void km_dispatch_wide(bool wide, A... a) {
+  if (wide) km_launch<TYPE, DERIV, true>(a...);
+  else km_launch<TYPE, DERIV, false>(a...);
+}
+template <int TYPE, class... A>
+void km_dispatch_deriv(int deriv, bool wide, A... a) {
+  if (deriv) km_dispatch_wide<TYPE, 1>(wide, a...);
+  else km_dispatch_wide<TYPE, 0>(wide, a...);
+}
+template <class... A>
+void km_dispatch(int type, int deriv, bool wide, A... a) {
+  switch (type) {
+    case 0: km_dispatch_deriv<0>(deriv, wide, a...); break;
+    case 1: km_dispatch_deriv<1>(deriv, wide, a...); break;
+    case 3: km_dispatch_deriv<3>(deriv, wide, a...); break;
+    default: km_dispatch_deriv<4>(deriv, wide, a...); break;
+  }
+}
+
 __global__ __launch_bounds__(KM_T) void coldots_kernel(const double* __restrict__ A, size_t lda, const double* __restrict__ B, size_t ldb,
                                                        long long n, double* __restrict__ out) {
   HSSK_SHARED double part[KM_T / 64];
@@ -254,11 +276,8 @@ extern "C" int hssk_kernel_matmul(hssk_ctx* ctx, const hssk_kernel_spec* spec, i
     hssk_set_error("hssk_kernel_matmul: the stage buffers do not fit the LDS of this device");
     return 2;
   }
-  // splits of the training points: whole stages, none empty
-  const long long stages = (n + KM_K - 1) / KM_K;
-  long long s = std::min<long long>(splits > 0 ? splits : hssk_kernel_matmul_splits(n), std::min<long long>(stages, 65535));
-  const long long per = ((stages + s - 1) / s) * KM_K;
-  s = (n + per - 1) / per;
+  const KmSplit sp = km_split_plan(n, KM_K, splits, hssk_kernel_matmul_splits(n));
+  const long long s = sp.s, per = sp.per;
   double* dst = out;
   size_t ldd = (size_t)ldo, slab = 0;
   if (s > 1) {
@@ -266,35 +285,10 @@ extern "C" int hssk_kernel_matmul(hssk_ctx* ctx, const hssk_kernel_spec* spec, i
     dst = ctx->kmm_slabs(sizeof(double) * slab * (size_t)s);
     ldd = (size_t)n;
   }
-  const int key = (spec->type << 2) | (deriv << 1) | (wide ? 1 : 0);
-  switch (key) {
-    case 0: km_launch<0, 0, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 1: km_launch<0, 0, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 2: km_launch<0, 1, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 3: km_launch<0, 1, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 4: km_launch<1, 0, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 5: km_launch<1, 0, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 6: km_launch<1, 1, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 7: km_launch<1, 1, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 12: km_launch<3, 0, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 13: km_launch<3, 0, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 14: km_launch<3, 1, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 15: km_launch<3, 1, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 16: km_launch<4, 0, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 17: km_launch<4, 0, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    case 18: km_launch<4, 1, false>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-    default: km_launch<4, 1, true>(ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s); break;
-  }
+  km_dispatch(spec->type, deriv, wide, ctx, *spec, B, (size_t)ldb, nc, dst, ldd, slab, per, (int)s);
   hssk_rt::check_launch();
-  if (s > 1) {
-    // the partials in split order; a padded output one column at a time
-    if (ldo == n) {
-      if (const int rc = hssk_sum_slabs(ctx, dst, (long long)slab, (long long)slab, (int)s, out)) return rc;
-    } else {
-      for (int c = 0; c < nc; c++)
-        if (const int rc = hssk_sum_slabs(ctx, dst + (size_t)c * n, n, (long long)slab, (int)s, out + (size_t)c * ldo)) return rc;
-    }
-  }
+  if (s > 1)
+    if (const int rc = km_reduce_splits(ctx, dst, n, nc, (int)s, out, ldo)) return rc;
   HSSK_API_END
 }
 

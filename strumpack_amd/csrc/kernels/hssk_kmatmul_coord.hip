@@ -24,6 +24,7 @@
 #include "hssk_device.h"
 #include "hssk_internal.h"
 #include "hssk_kpair.h"
+#include "hssk_kmatmul_split.h"
 #include "hssk_kmatmul_tile.h"
 
 namespace {
@@ -212,11 +213,8 @@ extern "C" int hssk_kernel_matmul_coord(hssk_ctx* ctx, const hssk_kernel_spec* s
     hssk_set_error("hssk_kernel_matmul_coord: the stage buffers do not fit the LDS of this device");
     return 2;
   }
-  // splits of the training points: whole stages, none empty (as hssk_kernel_matmul)
-  const long long stages = (n + KM_K - 1) / KM_K;
-  long long s = std::min<long long>(splits > 0 ? splits : hssk_kernel_matmul_splits(n), std::min<long long>(stages, 65535));
-  const long long per = ((stages + s - 1) / s) * KM_K;
-  s = (n + per - 1) / per;
+  const KmSplit sp = km_split_plan(n, KM_K, splits, hssk_kernel_matmul_splits(n));
+  const long long s = sp.s, per = sp.per;
   double* dst = out;
   size_t ldd = (size_t)ldo, slab = 0, cstride = (size_t)out_stride;
   if (s > 1) {   // the slabs of coordinate jj: s of them from dst + jj cstride on
@@ -228,18 +226,8 @@ extern "C" int hssk_kernel_matmul_coord(hssk_ctx* ctx, const hssk_kernel_spec* s
   if (spec->type == 0) kmc_dispatch<0>(nj, ctx, *spec, j0, B, (size_t)ldb, nc, dst, ldd, cstride, slab, per, (int)s);
   else kmc_dispatch<1>(nj, ctx, *spec, j0, B, (size_t)ldb, nc, dst, ldd, cstride, slab, per, (int)s);
   hssk_rt::check_launch();
-  if (s > 1) {
-    // the partials in split order; a padded output one column at a time
-    for (int jj = 0; jj < nj; jj++) {
-      const double* src = dst + (size_t)jj * cstride;
-      double* oj = out + (size_t)jj * (size_t)out_stride;
-      if (ldo == n) {
-        if (const int rc = hssk_sum_slabs(ctx, src, (long long)slab, (long long)slab, (int)s, oj)) return rc;
-      } else {
-        for (int c = 0; c < nc; c++)
-          if (const int rc = hssk_sum_slabs(ctx, src + (size_t)c * n, n, (long long)slab, (int)s, oj + (size_t)c * ldo)) return rc;
-      }
-    }
-  }
+  if (s > 1)
+    for (int jj = 0; jj < nj; jj++)
+      if (const int rc = km_reduce_splits(ctx, dst + (size_t)jj * cstride, n, nc, (int)s, out + (size_t)jj * (size_t)out_stride, ldo)) return rc;
   HSSK_API_END
 }

@@ -38,6 +38,7 @@
 #include "hssk_device.h"
 #include "hssk_internal.h"
 #include "hssk_kpair.h"
+#include "hssk_kmatmul_split.h"
 #include "hssk_matern.h"
 
 #include <cmath>
@@ -300,6 +301,18 @@ void kmf_launch(hssk_ctx* ctx, const KfArgs& a, int splits) {
   HSSK_LAUNCH((kmf_main_kernel<TYPE, KSM>), grid, dim3(256), KF_SHM, ctx->stream, a);
 }
 
+// the matrix-core depth of the instance: one per kf_ksm value
+template <int TYPE>
+void kf_dispatch(int ksm, hssk_ctx* ctx, const KfArgs& a, int splits) {
+  switch (ksm) {
+    case 2: kmf_launch<TYPE, 2>(ctx, a, splits); break;
+    case 5: kmf_launch<TYPE, 5>(ctx, a, splits); break;
+    case 9: kmf_launch<TYPE, 9>(ctx, a, splits); break;
+    case 17: kmf_launch<TYPE, 17>(ctx, a, splits); break;
+    default: kmf_launch<TYPE, 33>(ctx, a, splits); break;
+  }
+}
+
 void kmf_check_spec(const char* who, const hssk_ctx* ctx, const hssk_kernel_spec* spec) {
   if (!ctx || !spec) throw std::invalid_argument(std::string(who) + ": no context or kernel");
   check_spec(*spec);
@@ -359,10 +372,8 @@ extern "C" int hssk_kernel_matmul_f32(hssk_ctx* ctx, const hssk_kernel_spec* spe
   }
   const long long n = spec->n;
   const KfLayout L = kf_layout(n, spec->d);
-  // splits of the training points: whole stages, none empty
-  long long s = std::min<long long>(splits > 0 ? splits : hssk_kernel_matmul_f32_splits(n), std::min<long long>(L.nt, 65535));
-  const long long per = ((L.nt + s - 1) / s) * KF_T;
-  s = (n + per - 1) / per;
+  const KmSplit sp = km_split_plan(n, KF_T, splits, hssk_kernel_matmul_f32_splits(n));
+  const long long s = sp.s, per = sp.per;
   // context slabs: 256 bytes of statistics, then the split partials
   const size_t slab = s > 1 ? (size_t)n * nc : 0;
   char* work = (char*)ctx->kmm_slabs(256 + sizeof(double) * slab * (size_t)s);
@@ -382,35 +393,13 @@ extern "C" int hssk_kernel_matmul_f32(hssk_ctx* ctx, const hssk_kernel_spec* spe
     hssk_watch_start(ctx, 0);
   }
   const int ksm = kf_ksm(spec->d);
-  if (spec->type == 1) kmf_launch<1, 1>(ctx, a, (int)s);
-  else if (spec->type == 3) {
-    if (ksm == 2) kmf_launch<3, 2>(ctx, a, (int)s);
-    else if (ksm == 5) kmf_launch<3, 5>(ctx, a, (int)s);
-    else if (ksm == 9) kmf_launch<3, 9>(ctx, a, (int)s);
-    else if (ksm == 17) kmf_launch<3, 17>(ctx, a, (int)s);
-    else kmf_launch<3, 33>(ctx, a, (int)s);
-  } else if (spec->type == 4) {
-    if (ksm == 2) kmf_launch<4, 2>(ctx, a, (int)s);
-    else if (ksm == 5) kmf_launch<4, 5>(ctx, a, (int)s);
-    else if (ksm == 9) kmf_launch<4, 9>(ctx, a, (int)s);
-    else if (ksm == 17) kmf_launch<4, 17>(ctx, a, (int)s);
-    else kmf_launch<4, 33>(ctx, a, (int)s);
-  } else if (ksm == 2) kmf_launch<0, 2>(ctx, a, (int)s);
-  else if (ksm == 5) kmf_launch<0, 5>(ctx, a, (int)s);
-  else if (ksm == 9) kmf_launch<0, 9>(ctx, a, (int)s);
-  else if (ksm == 17) kmf_launch<0, 17>(ctx, a, (int)s);
-  else kmf_launch<0, 33>(ctx, a, (int)s);
+  if (spec->type == 1) kmf_launch<1, 1>(ctx, a, (int)s);   // (the difference form only: no matrix-core depth)
+  else if (spec->type == 3) kf_dispatch<3>(ksm, ctx, a, (int)s);
+  else if (spec->type == 4) kf_dispatch<4>(ksm, ctx, a, (int)s);
+  else kf_dispatch<0>(ksm, ctx, a, (int)s);
   hssk_rt::check_launch();
-  if (s > 1) {
-    // the partials in split order; a padded output one column at a time
-    const double* part = (const double*)(work + 256);
-    if (ldo == n) {
-      if (const int rc = hssk_sum_slabs(ctx, part, (long long)slab, (long long)slab, (int)s, out)) return rc;
-    } else {
-      for (int c = 0; c < nc; c++)
-        if (const int rc = hssk_sum_slabs(ctx, part + (size_t)c * n, n, (long long)slab, (int)s, out + (size_t)c * ldo)) return rc;
-    }
-  }
+  if (s > 1)
+    if (const int rc = km_reduce_splits(ctx, (const double*)(work + 256), n, nc, (int)s, out, ldo)) return rc;
   if (stats) {
     hssk_watch_stop(ctx, 0);
     long long hs[2] = {0, 0};
