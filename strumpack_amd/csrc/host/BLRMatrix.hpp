@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "DenseMatrix.hpp"
+#include "DevicePool.hpp"
 #include "StructuredMatrix.hpp"
 #include "StructuredOptions.hpp"
 #include "blr_engine.hpp"
@@ -189,7 +190,7 @@ template <> class BLRMatrix<double> : public structured::StructuredMatrix<double
     BLREngineOptions e;
     e.rel_tol = opts.rel_tol(); e.abs_tol = opts.abs_tol(); e.max_rank = opts.max_rank(); e.verbose = opts.verbose();
     e.lr_algo = opts.low_rank_algorithm() == LowRankAlgorithm::ACA ? 1 : 0;
-    if (const char* d = std::getenv("STRUMPACK_AMD_DEVICE")) e.device = std::atoi(d);
+    e.device = device_from_env();
     std::shared_ptr<DeviceBLR> eng(new DeviceBLR(int(ds + du), tiles, int(ds + du), tiles, e));
     std::vector<char> adm(tiles1.size() * tiles1.size());
     for (std::size_t j = 0; j < tiles1.size(); j++)
@@ -278,7 +279,7 @@ template <> class BLRMatrix<double> : public structured::StructuredMatrix<double
     BLREngineOptions e;
     e.rel_tol = o.rel_tol(); e.abs_tol = o.abs_tol(); e.max_rank = o.max_rank(); e.verbose = o.verbose();
     e.lr_algo = o.low_rank_algorithm() == LowRankAlgorithm::ACA ? 1 : 0;
-    if (const char* d = std::getenv("STRUMPACK_AMD_DEVICE")) e.device = std::atoi(d);
+    e.device = device_from_env();
     eng_.reset(new DeviceBLR(int(m_), rt_, int(n_), ct_, e));
     part_ = 0;
   }

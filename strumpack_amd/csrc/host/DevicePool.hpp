@@ -13,6 +13,12 @@
 
 namespace strumpack {
 
+// the HIP device the engines of this process use: STRUMPACK_AMD_DEVICE, read at every call (0 without it)
+inline int device_from_env() {
+  const char* e = std::getenv("STRUMPACK_AMD_DEVICE");
+  return e ? std::atoi(e) : 0;
+}
+
 class DevicePool {
  public:
   static DevicePool& get() { static DevicePool p; return p; }

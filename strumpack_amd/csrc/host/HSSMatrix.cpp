@@ -7,6 +7,7 @@
 #include <mutex>
 #include <exception>
 #include "HSSMatrix.hpp"
+#include "DevicePool.hpp"
 #include "Kernel.hpp"
 #include "NeighborSearch.hpp"
 
@@ -33,7 +34,7 @@ EngineOptions HSSMatrix<double>::engine_options(const opts_t& o) {
   e.factor_ahead = o.factor_ahead();
   e.symmetric = o.symmetric_operand();
   if (const char* fa = std::getenv("STRUMPACK_AMD_FACTOR_AHEAD")) e.factor_ahead = std::atoi(fa) != 0;
-  if (const char* d = std::getenv("STRUMPACK_AMD_DEVICE")) e.device = std::atoi(d);
+  e.device = device_from_env();
   return e;
 }
 

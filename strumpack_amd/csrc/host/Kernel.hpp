@@ -212,7 +212,7 @@ template <> class Kernel<double> {
   virtual scalar_t eval_kernel_function(const scalar_t* x, const scalar_t* y) const = 0;
 
  private:
-  struct Model;   // HSS matrix, device points, labels, weights (Kernel.cpp)
+  struct Model;   // HSS matrix, device points, labels, weights (KernelModel.hpp)
   std::unique_ptr<Model> model_;
   bool keep_model_ = false;
   mutable double var_ms_[3] = {0., 0., 0.};
@@ -222,7 +222,11 @@ template <> class Kernel<double> {
   KrylovInner inner_ = KrylovInner::FP64;
   scalar_t inner_rtol_ = KRYLOV_INNER_RTOL_DEFAULT;
   const Model& model(const char* what) const;
-  struct KrylovWork;   // the device blocks of a Krylov call (Kernel.cpp)
+  // the prologue of both gradients (KernelGradient.cpp): the model after the checks of the probes Z (and of d() <= dmax where dmax
+  // is given); the block model_probes(m, seed) after the checks of the seeded form
+  const Model& check_probes(const char* what, const DenseM_t& Z, std::size_t dmax = 0) const;
+  DenseM_t seeded_probes(const char* what, int m, unsigned long long seed) const;
+  struct KrylovWork;   // the device blocks of a Krylov call (KernelModel.hpp)
   const Model& krylov_model(const char* what, scalar_t rtol, int maxit, int restart) const;
   // one block of at most 64 columns: dX (first iterate in, last iterate out) and dB are n x nc device blocks, leading dimension n
   void krylov_block(const Model& M, KrylovWork& ws, int nc, double* dX, const double* dB, scalar_t rtol, int maxit, int restart,
@@ -364,7 +368,7 @@ template <> class Kernel<float> {
   virtual scalar_t eval_kernel_function(const scalar_t* x, const scalar_t* y) const = 0;
 
  private:
-  struct Resident;   // device context, points and weights in HBM (Kernel.cpp)
+  struct Resident;   // device context, points and weights in HBM (KernelFloat.cpp)
   mutable std::unique_ptr<Resident> res_;
   mutable long long pstats_[6] = {0, 0, 0, 0, 0, 0};
   void run_predict(int m, const scalar_t* test_host, int ldt, const scalar_t* test_dev, const scalar_t* weights_host,

@@ -361,9 +361,7 @@ int SPX_comm_selftest(SPXComm comm) {
   if (!c) throw std::invalid_argument("null communicator");
   const int G = c->world(), me = c->rank(), L = 1000;
   hssk_ctx* ctx = nullptr;
-  int dev = 0;
-  if (const char* e = std::getenv("STRUMPACK_AMD_DEVICE")) dev = std::atoi(e);   // (the device the engines of this process use)
-  if (hssk_ctx_create(&ctx, dev)) throw std::runtime_error(hssk_last_error());
+  if (hssk_ctx_create(&ctx, device_from_env())) throw std::runtime_error(hssk_last_error());
   struct Guard { hssk_ctx* c; std::vector<void*> p; ~Guard() { for (void* q : p) hssk_free(q); hssk_ctx_destroy(c); } } g{ctx, {}};
   auto dmal = [&](size_t n) { void* p = hssk_malloc((long long)(sizeof(double) * n)); if (!p) throw std::runtime_error("selftest: allocation failed"); g.p.push_back(p); return (double*)p; };
   void* stream = hssk_ctx_stream(ctx);
@@ -603,7 +601,7 @@ std::unique_ptr<BLR::DeviceBLR> make_front(int dsep, int dupd, int nt1, const in
   e.max_rank = opts ? opts->max_rank : d.max_rank();
   e.lr_algo = g_blr_low_rank_algorithm;
   e.verbose = opts && opts->verbose;
-  if (const char* dv = std::getenv("STRUMPACK_AMD_DEVICE")) e.device = std::atoi(dv);
+  e.device = device_from_env();
   std::unique_ptr<BLR::DeviceBLR> f(new BLR::DeviceBLR(dsep + dupd, tiles, dsep + dupd, tiles, e));
   f->time_phases = g_blr_time_phases;
   return f;
