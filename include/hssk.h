@@ -230,8 +230,8 @@ int hssk_leaf_update_vbatched(hssk_ctx* ctx, const hssk_leaf_update_desc* descs,
  * Euclidean distance r, with s = sqrt(2 nu) r / h -- type 3: Matern32, (1 + s) e^-s, nu = 3/2; type 4: Matern52,
  * (1 + s + s^2 / 3) e^-s, nu = 5/2 -- evaluated from the squared distance (the Gauss distance loop, then
  * csrc/kernels/hssk_matern.h); a pair at distance 0 gives exactly 1.  Types 3 and 4 are taken by the sums and products over all
- * pairs -- hssk_kernel_predict, hssk_kernel_cross, hssk_kernel_predict_cols, hssk_kernel_matmul, hssk_kernel_matmul_f32 (and its
- * prep), hssk_matern_predict_f32 (and _wide) -- at any d those take.  The construction kernels (hssk_kernel_eval_vbatched,
+ * pairs -- hssk_kernel_predict, hssk_kernel_cross, hssk_kernel_predict_cols, hssk_kernel_predict_grad, hssk_kernel_matmul,
+ * hssk_kernel_matmul_f32 (and its prep), hssk_matern_predict_f32 (and _wide) -- at any d those take.  The construction kernels (hssk_kernel_eval_vbatched,
  * hssk_gram_gen_vbatched) and with them the kernel ridge regression fit do NOT take them yet: they return 2 and write nothing. */
 typedef struct hssk_kernel_spec {
   const double* X;
@@ -298,6 +298,21 @@ int hssk_kernel_cross(hssk_ctx* ctx, const hssk_kernel_spec* spec, const double*
  * With W = (K + lambda I)^-1 k(X, T) this is the quadratic form of the predictive variance. */
 int hssk_kernel_predict_cols(hssk_ctx* ctx, const hssk_kernel_spec* spec, const double* W, long long ldw, const double* T, int m,
                              double* pred);
+/* G(j, c) = sum_r w_rc dk(x_r, t_c) / dt_cj, j < d, c < m: the gradient of the prediction sum in the test points (T: d x m, device; G:
+ * d x m column-major, ldg >= d; the rows d .. ldg - 1 and the columns >= m are not touched).  ldw == 0: one weight
+ * vector, w_rc = W[r]; ldw >= n: a weight column per test point, w_rc = W(r, c).  Types 0, 1, 3 and 4, d <= 64.  With
+ * delta = x_r - t_c the derivative of a pair is f delta_j -- f = k / h^2 (Gauss), (3 / h^2) e^-s (Matern32),
+ * (5 / (3 h^2)) (1 + s) e^-s (Matern52) -- or f sign(delta_j), f = k / h, sign(0) = 0 (Laplace): no division by the distance, a pair
+ * of equal points adds exactly 0, a Laplace pair that agrees in coordinate j exactly 0 to that coordinate; k, s and the exponentials
+ * are those of hssk_kernel_predict.  The training points are split across workgroups: splits = 0 takes
+ * hssk_kernel_predict_grad_splits(n, m), a positive value forces the count (at most one split per 64 training points).  Split
+ * partials go to slabs the context keeps and are added in split order; no atomics, bitwise repeatable, and with the same forced
+ * count a column of G does not depend on m, on the other test points or on its position.  m == 0: nothing is done; n == 0: zeros.
+ * Returns HSSK_UNSUPPORTED (2) for ANOVA and d > 64, 1 for a null pointer, m < 0, ldg < d, 0 < ldw < n, ldw < 0, splits < 0 or a
+ * type outside 0 .. 4; a refused call writes nothing. */
+int hssk_kernel_predict_grad(hssk_ctx* ctx, const hssk_kernel_spec* spec, const double* W, long long ldw, const double* T, int m,
+                             double* G, long long ldg, int splits);
+int hssk_kernel_predict_grad_splits(long long n, int m);   /* what splits = 0 takes: a function of (n, m) alone */
 /* The promise of the single-precision prediction's matrix-core route: the worst relative error the norm expansion
  * |x|^2 + |t|^2 - 2 x.t can add to a term w_r k(x_r, t_c).  A (training tile, test tile) pair whose scaled norms would exceed it,
  * 4 (d + 4) 2^-24 (max |x~|^2 + max |t~|^2) > tau, is computed from FP32 differences instead. */

@@ -139,6 +139,20 @@ int SPX_kernel_krylov_inner(STRUMPACKKernel K, int* precision, double* inner_rto
 /* of the last of the three calls: out[0] FP64 products, [1] FP32 products, [2] fallbacks, [3] cycles, [4] ms of the FP64 products,
  * [5] ms of the FP32 products.  Refused like SPX_kernel_krylov_ms. */
 int SPX_kernel_krylov_stats(STRUMPACKKernel K, double out[6]);
+/* ---- gradients in the test points (double handles, Gauss and Laplace, d <= 64).  test: d x m, grad: d x m (one
+ * gradient per column, in the coordinates of the points the handle was created with).  Every call returns non-zero, its outputs
+ * untouched, for a float handle, an ANOVA or user-defined kernel, d > 64 and a handle that has not been fitted.
+ * grad(j, c) = d prediction(t_c) / dt_cj = sum_r alpha_r dk(x_r, t_c) / dt_cj with the handle's weights: the gradient of
+ * STRUMPACK_kernel_predict_double (a force, where the fit is an energy surface).  No kept model needed. */
+int SPX_kernel_predict_gradient_double(STRUMPACKKernel K, int m, const double* test, double* grad);
+/* SPX_kernel_predict_variance_double with grad(:, c) = -2 sum_r V(r, c) dk(x_r, t_c) / dt_c, V = H^-1 k(X, T) (d k(t, t) / dt = 0): var
+ * is bit for bit what SPX_kernel_predict_variance_double returns.  grad is the derivative of var exactly when H is symmetric;
+ * otherwise it is -2 D^T H^-1 k, D the derivative of k(X, t) in t.  Also refused without a kept model. */
+int SPX_kernel_predict_variance_gradient_double(STRUMPACKKernel K, int m, const double* test, double* var, double* grad);
+/* the same with the exact solve: var is bit for bit what SPX_kernel_predict_variance_exact_double returns; arguments, info and
+ * refusals as there (SPX_kernel_set_krylov_inner is respected; the gradient sum itself is always FP64) */
+int SPX_kernel_predict_variance_gradient_exact_double(STRUMPACKKernel K, int m, const double* test, double* var, double* grad, double rtol,
+                                                      int maxit, int restart, double* info);
 /* binary_tree_clustering on its own (clustering/Clustering.hpp:143-168): algo 0 natural, 1 2means, 2 kdtree,
  * 3 pca, 4 cobble; data (d x n) is reordered in place, perm is 1-based; returns the number of leaves and writes
  * at most cap leaf sizes */

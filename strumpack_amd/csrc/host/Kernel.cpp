@@ -1,7 +1,9 @@
-// Kernel<double>::fit_HSS / predict (reference: kernel/KernelRegression.hpp:56-123), the kept model and its predictive variance.
-// The gradients are in KernelGradient.cpp, the solves with the exact kernel matrix in KernelKrylov.cpp, Kernel<float> in
-// KernelFloat.cpp and the C interface of include/kernel/Kernel.h in KernelC.cpp.
+// Kernel<double>::fit_HSS / predict (reference: kernel/KernelRegression.hpp:56-123), the kept model and its predictive variance,
+// and the gradients of both predictions in the test points.  The gradients of the likelihood are in KernelGradient.cpp, the
+// solves with the exact kernel matrix in KernelKrylov.cpp, Kernel<float> in KernelFloat.cpp and the C interface of
+// include/kernel/Kernel.h in KernelC.cpp.
 #include <chrono>
+#include <optional>
 
 #include "KernelModel.hpp"
 
@@ -60,14 +62,30 @@ std::vector<double> Kernel<double>::predict_variance(const DenseMatrix<double>& 
   return variance_chunks(M, test, nullptr, 0., 0, 0, nullptr);
 }
 
+void Kernel<double>::require_point_gradient(const char* what) const {
+  if (device_type() != 0 && device_type() != 1) throw std::invalid_argument(std::string(what) + ": Gauss and Laplace kernels only");
+  if (d() > 64) throw std::invalid_argument(std::string(what) + ": at most 64 coordinates");
+}
+
+std::vector<double> Kernel<double>::predict_variance_gradient(const DenseMatrix<double>& test, DenseMatrix<double>& grad) const {
+  const Model& M = model("predict_variance_gradient");
+  require_point_gradient("predict_variance_gradient");
+  if (test.rows() != d()) throw std::invalid_argument("predict_variance_gradient: test points have the wrong dimension");
+  return variance_chunks(M, test, nullptr, 0., 0, 0, nullptr, &grad);
+}
+
 std::vector<double> Kernel<double>::variance_chunks(const Model& M, const DenseMatrix<double>& test, KrylovWork* ws, double rtol, int maxit, int restart,
-                                                    KrylovInfo* info) const {
+                                                    KrylovInfo* info, DenseMatrix<double>* grad) const {
   const int m = int(test.cols()), dim = int(d()), CH = 64;
   const long long nn = (long long)n();
   std::vector<double> var(m, 0.);
   var_ms_[0] = var_ms_[1] = var_ms_[2] = 0.;
+  if (grad) *grad = DenseMatrix<double>(dim, m);
   if (m == 0) return var;
   hssk_ctx* ctx = M.ctx();
+  std::optional<PoolBuf> bG;   // (only where a gradient is asked for: the variance calls acquire what they always did)
+  if (grad) bG.emplace(ctx, sizeof(double) * dim * m);
+  double* dG = grad ? (double*)bG->p : nullptr;
   PoolBuf bT(ctx, sizeof(double) * dim * m), bK(ctx, sizeof(double) * nn * CH), bD(ctx, sizeof(double) * CH * CH), bP(ctx, sizeof(double) * m);
   double *dT = (double*)bT.p, *dK = (double*)bK.p, *dD = (double*)bD.p, *dP = (double*)bP.p;
   ckk(hssk_memcpy2d_h2d(ctx, dT, sizeof(double) * dim, test.data(), sizeof(double) * test.ld(), sizeof(double) * dim, m));
@@ -88,10 +106,17 @@ std::vector<double> Kernel<double>::variance_chunks(const Model& M, const DenseM
       krylov_block(M, *ws, mc, dK, ws->B, rtol, maxit, restart, *info);
     }
     watched(ctx, 3, [&] { ckk(hssk_kernel_predict_cols(ctx, &spec, dK, nn, dTc, mc, dP + c0)); });
+    // dK holds V = H^-1 k (or its refinement): the gradient sum with a weight column per test point
+    if (grad) ckk(hssk_kernel_predict_grad(ctx, &spec, dK, nn, dTc, mc, dG + (size_t)c0 * dim, dim, 0));
   }
   ckk(hssk_memcpy_d2h(ctx, quad.data(), dP, (long long)sizeof(double) * m));
   for (int w = 0; w < 3; w++) var_ms_[w] = hssk_watch_read_ms(ctx, w + 1, nullptr);
   for (int c = 0; c < m; c++) var[c] = ktt[c] - quad[c];
+  if (grad) {
+    ckk(hssk_memcpy_d2h(ctx, grad->data(), dG, (long long)sizeof(double) * dim * m));
+    for (int c = 0; c < m; c++)
+      for (int j = 0; j < dim; j++) (*grad)(j, c) *= -2.;
+  }
   return var;
 }
 
@@ -141,10 +166,37 @@ DenseMatrix<double> Kernel<double>::fit_HSS(std::vector<double>& labels, const H
   return weights;
 }
 
+namespace {
+// The scaffolding of predict and predict_gradient: a context and four buffers of the call's own (not the pool's) -- the points, the
+// test points, the weights and `count` doubles of output --, then call(ctx, spec, weights, test points, output) and the output
+// copied to `out`.  The buffers go first, then the context, on either way out.
+template <class F>
+void on_own_device(const Kernel<double>& K, const DenseMatrix<double>& test, const DenseMatrix<double>& weights, std::size_t count, double* out,
+                   F&& call) {
+  const int m = int(test.cols()), dim = int(K.d());
+  const long long n = (long long)K.n();
+  hssk_ctx* ctx = nullptr;
+  ckk(hssk_ctx_create(&ctx, device_from_env()));
+  struct Own { hssk_ctx* ctx; void* p[4]; ~Own() { for (void* q : p) hssk_free(q); hssk_ctx_destroy(ctx); } } own{ctx, {nullptr, nullptr, nullptr, nullptr}};
+  auto dalloc = [&own](int i, long long bytes) { if (!(own.p[i] = hssk_malloc(bytes))) throw std::runtime_error(hssk_last_error()); return own.p[i]; };
+  void* dX = dalloc(0, (long long)sizeof(double) * dim * n);
+  void* dT = dalloc(1, (long long)sizeof(double) * dim * m);
+  void* dw = dalloc(2, (long long)sizeof(double) * n);
+  void* dp = dalloc(3, (long long)sizeof(double) * count);
+  ckk(hssk_memcpy2d_h2d(ctx, dX, sizeof(double) * dim, K.data().data(), sizeof(double) * K.data().ld(), sizeof(double) * dim, n));
+  ckk(hssk_memcpy2d_h2d(ctx, dT, sizeof(double) * dim, test.data(), sizeof(double) * test.ld(), sizeof(double) * dim, m));
+  ckk(hssk_memcpy_h2d(ctx, dw, weights.data(), (long long)sizeof(double) * n));
+  hssk_kernel_spec spec{(const double*)dX, n, dim, K.device_type(), K.degree(), K.width(), 0.};
+  call(ctx, spec, (const double*)dw, (const double*)dT, (double*)dp);
+  ckk(hssk_memcpy_d2h(ctx, out, dp, (long long)sizeof(double) * count));
+  ckk(hssk_sync(ctx));
+}
+}  // namespace
+
 std::vector<double> Kernel<double>::predict(const DenseMatrix<double>& test, const DenseMatrix<double>& weights) const {
   if (test.rows() != d()) throw std::invalid_argument("predict: test points have the wrong dimension");
   if (weights.rows() != n()) throw std::invalid_argument("predict: one weight per training point expected");
-  const int m = int(test.cols()), dim = int(d());
+  const int m = int(test.cols());
   std::vector<double> prediction(m, 0.);
   if (m == 0) return prediction;
   if (device_type() < 0) {
@@ -156,23 +208,24 @@ std::vector<double> Kernel<double>::predict(const DenseMatrix<double>& test, con
     }
     return prediction;
   }
-  // a context and four buffers of the call's own (not the pool's): the buffers go first, then the context, on either way out
-  hssk_ctx* ctx = nullptr;
-  ckk(hssk_ctx_create(&ctx, device_from_env()));
-  struct Own { hssk_ctx* ctx; void* p[4]; ~Own() { for (void* q : p) hssk_free(q); hssk_ctx_destroy(ctx); } } own{ctx, {nullptr, nullptr, nullptr, nullptr}};
-  auto dalloc = [&own](int i, long long bytes) { if (!(own.p[i] = hssk_malloc(bytes))) throw std::runtime_error(hssk_last_error()); return own.p[i]; };
-  void* dX = dalloc(0, (long long)sizeof(double) * dim * n());
-  void* dT = dalloc(1, (long long)sizeof(double) * dim * m);
-  void* dw = dalloc(2, (long long)sizeof(double) * n());
-  void* dp = dalloc(3, (long long)sizeof(double) * m);
-  ckk(hssk_memcpy2d_h2d(ctx, dX, sizeof(double) * dim, data_.data(), sizeof(double) * data_.ld(), sizeof(double) * dim, (long long)n()));
-  ckk(hssk_memcpy2d_h2d(ctx, dT, sizeof(double) * dim, test.data(), sizeof(double) * test.ld(), sizeof(double) * dim, m));
-  ckk(hssk_memcpy_h2d(ctx, dw, weights.data(), (long long)sizeof(double) * n()));
-  hssk_kernel_spec spec{(const double*)dX, (long long)n(), dim, device_type(), degree(), width(), 0.};
-  ckk(hssk_kernel_predict(ctx, &spec, (const double*)dw, (const double*)dT, m, (double*)dp));
-  ckk(hssk_memcpy_d2h(ctx, prediction.data(), dp, (long long)sizeof(double) * m));
-  ckk(hssk_sync(ctx));
+  on_own_device(*this, test, weights, m, prediction.data(), [&](hssk_ctx* ctx, const hssk_kernel_spec& spec, const double* dw, const double* dT, double* dp) {
+    ckk(hssk_kernel_predict(ctx, &spec, dw, dT, m, dp));
+  });
   return prediction;
+}
+
+DenseMatrix<double> Kernel<double>::predict_gradient(const DenseMatrix<double>& test, const DenseMatrix<double>& weights) const {
+  require_point_gradient("predict_gradient");
+  if (test.rows() != d()) throw std::invalid_argument("predict_gradient: test points have the wrong dimension");
+  if (weights.rows() != n()) throw std::invalid_argument("predict_gradient: one weight per training point expected");
+  const int m = int(test.cols()), dim = int(d());
+  DenseMatrix<double> grad(dim, m);
+  if (m == 0) return grad;
+  on_own_device(*this, test, weights, (std::size_t)dim * m, grad.data(),
+                [&](hssk_ctx* ctx, const hssk_kernel_spec& spec, const double* dw, const double* dT, double* dG) {
+                  ckk(hssk_kernel_predict_grad(ctx, &spec, dw, 0, dT, m, dG, dim, 0));
+                });
+  return grad;
 }
 
 const long long* last_fit_info() { return last_fit.v; }

@@ -117,6 +117,15 @@ template <> class Kernel<double> {
   // for the observation noise).  Not clamped: H is K + lambda I only up to the compression tolerance, so a value may come out
   // slightly negative.  Chunks of 64 test points: cross-kernel block, device solve in place, column-weighted sum.
   std::vector<scalar_t> predict_variance(const DenseM_t& test) const;
+  // ---- extension: gradients in the test points (hssk_kernel_predict_grad).  Gauss and Laplace, d <= 64; every call
+  // throws for a user-defined kernel, an ANOVA kernel and d > 64.
+  // grad(j, c) = sum_r weights(r) dk(x_r, t_c) / dt_cj, d x m: the gradient of predict in the test points (no kept model needed)
+  DenseM_t predict_gradient(const DenseM_t& test, const DenseM_t& weights) const;
+  // predict_variance with grad(:, c) = -2 sum_r V(r, c) dk(x_r, t_c) / dt_c, V = H^-1 k(X, T) the solved columns of the chunk (the
+  // term dk(t, t) / dt is 0 for these stationary kernels); grad is resized to d x m.  This is the derivative of the returned variance
+  // exactly when H is symmetric; otherwise it is -2 D^T H^-1 k, D the derivative of k(X, t) in t.  The variances returned are bit
+  // for bit those of predict_variance.
+  std::vector<scalar_t> predict_variance_gradient(const DenseM_t& test, DenseM_t& grad) const;
   // a new lambda without a new compression: shift(lambda - current), factor, solve of the kept labels; returns the new weights,
   // which the model keeps, and lambda() is the new one afterwards
   DenseM_t model_set_lambda(scalar_t lambda);
@@ -170,6 +179,11 @@ template <> class Kernel<double> {
   // to rtol.  Not clamped.
   std::vector<scalar_t> predict_variance_exact(const DenseM_t& test, KrylovInfo* info = nullptr, scalar_t rtol = 1e-8, int maxit = 100,
                                                int restart = 30) const;
+  // predict_variance_gradient with the exact solve: V = (K + lambda I)^-1 k(X, T) up to rtol (K is symmetric: the derivative of the
+  // returned variance up to rtol).  The variances are bit for bit those of predict_variance_exact; krylov_inner is respected as
+  // there, the gradient sum itself is always FP64.
+  std::vector<scalar_t> predict_variance_gradient_exact(const DenseM_t& test, DenseM_t& grad, KrylovInfo* info = nullptr, scalar_t rtol = 1e-8,
+                                                        int maxit = 100, int restart = 30) const;
   // device-clock milliseconds of the last of these three calls: exact products, ULV solves, Krylov kernels (profiling)
   const double* krylov_ms() const { return kry_ms_; }
   // ---- extension: mixed precision for these three calls.  Handle state, set like keep_model; FP64 is the default
@@ -235,9 +249,12 @@ template <> class Kernel<double> {
   // bytes of the prepared float points a call's work buffers carry (0 in FP64 mode), and their preparation
   std::size_t krylov_prep_bytes() const;
   void krylov_prepare(const Model& M, KrylovWork& ws) const;
-  // the chunk loop of both variance calls; ws == nullptr: the compressed solve
+  // the chunk loop of the variance calls; ws == nullptr: the compressed solve; grad != nullptr: also the gradient in the test
+  // points (resized to d x m), from the chunk's solved columns
   std::vector<scalar_t> variance_chunks(const Model& M, const DenseM_t& test, KrylovWork* ws, scalar_t rtol, int maxit, int restart,
-                                        KrylovInfo* info) const;
+                                        KrylovInfo* info, DenseM_t* grad = nullptr) const;
+  // what the gradients in the test points take: throws for a user-defined or ANOVA kernel and for d > 64
+  void require_point_gradient(const char* what) const;
 };
 
 template <typename scalar_t> class GaussKernel;

@@ -326,6 +326,40 @@ int SPX_kernel_predict_variance_exact_double(STRUMPACKKernel K, int m, const dou
     return 0;
   });
 }
+// ---- gradients in the test points ----
+int SPX_kernel_predict_gradient_double(STRUMPACKKernel K, int m, const double* test, double* grad) {
+  return guarded([&] {
+    auto k = builtin_of(K);
+    if (!k || k->device_type() > 1 || k->d() > 64 || handle(K)->weights.rows() != k->n()) return 1;
+    if (m < 0 || (m > 0 && (!test || !grad))) return 1;
+    const DenseMatrix<double> g = k->predict_gradient(DenseMatrix<double>(k->d(), m, test, k->d()), handle(K)->weights);
+    std::copy(g.data(), g.data() + k->d() * (std::size_t)m, grad);
+    return 0;
+  });
+}
+int SPX_kernel_predict_variance_gradient_double(STRUMPACKKernel K, int m, const double* test, double* var, double* grad) {
+  return with_model(K, [&](KernelD& k) {
+    if (m < 0 || (m > 0 && (!test || !var || !grad))) return 1;
+    DenseMatrix<double> g;
+    const std::vector<double> v = k.predict_variance_gradient(DenseMatrix<double>(k.d(), m, test, k.d()), g);
+    std::copy(v.begin(), v.end(), var);
+    std::copy(g.data(), g.data() + k.d() * (std::size_t)m, grad);
+    return 0;
+  });
+}
+int SPX_kernel_predict_variance_gradient_exact_double(STRUMPACKKernel K, int m, const double* test, double* var, double* grad, double rtol,
+                                                      int maxit, int restart, double* info) {
+  return with_model(K, [&](KernelD& k) {
+    if (m < 0 || (m > 0 && (!test || !var || !grad))) return 1;
+    kernel::KrylovInfo I;
+    DenseMatrix<double> g;
+    const std::vector<double> v = k.predict_variance_gradient_exact(DenseMatrix<double>(k.d(), m, test, k.d()), g, &I, rtol, maxit, restart);
+    std::copy(v.begin(), v.end(), var);
+    std::copy(g.data(), g.data() + k.d() * (std::size_t)m, grad);
+    krylov_info_out(I, info);
+    return 0;
+  });
+}
 int SPX_kernel_set_krylov_inner(STRUMPACKKernel K, int precision, double inner_rtol) {
   return guarded([&] {
     auto k = builtin_of(K);

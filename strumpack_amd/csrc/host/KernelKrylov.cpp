@@ -225,5 +225,20 @@ std::vector<double> Kernel<double>::predict_variance_exact(const DenseMatrix<dou
   return var;
 }
 
+std::vector<double> Kernel<double>::predict_variance_gradient_exact(const DenseMatrix<double>& test, DenseMatrix<double>& grad, KrylovInfo* info,
+                                                                    double rtol, int maxit, int restart) const {
+  const Model& M = krylov_model("predict_variance_gradient_exact", rtol, maxit, restart);
+  require_point_gradient("predict_variance_gradient_exact");
+  if (test.rows() != d()) throw std::invalid_argument("predict_variance_gradient_exact: test points have the wrong dimension");
+  KrylovInfo local;
+  if (test.cols() == 0) { grad = DenseMatrix<double>(d(), 0); if (info) *info = local; return {}; }
+  KrylovWork ws(M.ctx(), (long long)n(), 64, maxit, restart, false, krylov_prep_bytes());
+  krylov_prepare(M, ws);
+  std::vector<double> var = variance_chunks(M, test, &ws, rtol, maxit, restart, &local, &grad);
+  krylov_finish(M, local);
+  if (info) *info = local;
+  return var;
+}
+
 }  // namespace kernel
 }  // namespace strumpack

@@ -21,6 +21,15 @@ __device__ inline double hssk_matern(double q, double c, double h) {
   if (DERIV == 0) return TYPE == 3 ? (1. + s) * e : (1. + s + s * s / 3.) * e;
   return TYPE == 3 ? s * s * e / h : s * s * (1. + s) * e / (3. * h);
 }
+// The factor f of the derivative in a point, dk(x, t)/dt_j = f (x_j - t_j): dk/ds = -s e^-s (nu = 3/2), -s (1 + s) e^-s / 3
+// (nu = 5/2) and ds/dt_j = -c (x_j - t_j) / s, so the s cancels and nothing divides by the distance:
+//   type 3:  f = c e^-s        type 4:  f = (c / 3) (1 + s) e^-s        with the s and the exponential of hssk_matern above
+template <int TYPE>
+__device__ inline double hssk_matern_dt_factor(double q, double c) {
+  static_assert(TYPE == 3 || TYPE == 4, "Matern32 is type 3, Matern52 type 4");
+  const double s = sqrt(c * q), e = exp(-s);
+  return TYPE == 3 ? c * e : (c / 3.) * ((1. + s) * e);
+}
 // the same with the type known only at run time (kernels that are not instantiated per type)
 __device__ inline double hssk_matern_rt(int type, double q, double c, double h) {
   return type == 3 ? hssk_matern<3, 0>(q, c, h) : hssk_matern<4, 0>(q, c, h);

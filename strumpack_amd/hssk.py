@@ -172,6 +172,7 @@ HSSK_SYMBOLS = [
     "hssk_kernel_predict_f32", "hssk_kernel_predict_f32_wide", "hssk_kernel_predict_splits",
     "hssk_matern_predict_f32", "hssk_matern_predict_f32_wide",
     "hssk_logabsdet_vbatched", "hssk_kernel_cross", "hssk_kernel_predict_cols",
+    "hssk_kernel_predict_grad", "hssk_kernel_predict_grad_splits",
     "hssk_kernel_matmul", "hssk_kernel_matmul_splits", "hssk_coldots",
     "hssk_kernel_matmul_coord", "hssk_kernel_matmul_coord_max", "hssk_kernel_matmul_coord_group",
     "hssk_krylov_start", "hssk_krylov_orth", "hssk_krylov_combine",
@@ -301,6 +302,10 @@ class Hssk:
         L.hssk_logabsdet_vbatched.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.hssk_kernel_cross.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
         L.hssk_kernel_predict_cols.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p]
+        # the gradient of the prediction sum in the test points: W, ldw (0: one weight vector), T, m, G, ldg, splits
+        L.hssk_kernel_predict_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_longlong, C.c_int]
+        L.hssk_kernel_predict_grad_splits.argtypes = [C.c_longlong, C.c_int]
         L.hssk_kernel_matmul.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong,
                                          C.c_int]
         L.hssk_kernel_matmul_splits.argtypes = [C.c_longlong]

@@ -16,6 +16,8 @@ KERNEL_SYMBOLS = [
     "SPX_kernel_model_points", "SPX_kernel_lml_gradient", "SPX_kernel_lml_gradient_coords", "SPX_kernel_model_probes", "SPX_kernel_model_residual",
     "SPX_kernel_gradient_ms", "SPX_kernel_model_refine", "SPX_kernel_model_solve", "SPX_kernel_predict_variance_exact_double",
     "SPX_kernel_krylov_ms", "SPX_kernel_set_krylov_inner", "SPX_kernel_krylov_inner", "SPX_kernel_krylov_stats",
+    "SPX_kernel_predict_gradient_double", "SPX_kernel_predict_variance_gradient_double",
+    "SPX_kernel_predict_variance_gradient_exact_double",
 ]
 KRYLOV_INNER = {"f64": 0, "f32": 1}
 KERNEL_TYPES = {"Gauss": 0, "rbf": 0, "Laplace": 1, "ANOVA": 2}
@@ -61,6 +63,9 @@ def load(path):
     L.SPX_kernel_model_refine.argtypes = [vp, C.c_double, C.c_int, C.c_int, vp]
     L.SPX_kernel_model_solve.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp]
     L.SPX_kernel_predict_variance_exact_double.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, vp]
+    L.SPX_kernel_predict_gradient_double.argtypes = [vp, C.c_int, vp, vp]
+    L.SPX_kernel_predict_variance_gradient_double.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.SPX_kernel_predict_variance_gradient_exact_double.argtypes = [vp, C.c_int, vp, vp, vp, C.c_double, C.c_int, C.c_int, vp]
     L.SPX_kernel_krylov_ms.argtypes = [vp, vp]
     L.SPX_kernel_set_krylov_inner.argtypes = [vp, C.c_int, C.c_double]
     L.SPX_kernel_krylov_inner.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
@@ -152,6 +157,50 @@ class KernelRegression:
                 raise RuntimeError("SPX_kernel_predict_variance_exact_double failed (a kept model of a Gauss or Laplace fit and valid "
                                    "rtol / maxit / restart are needed; inner=\"f32\": at most 64 coordinates)")
             return (out, self._krylov_stats(self._krylov_info(buf))) if info else out
+
+    # ---- gradients in the test points (double fits, Gauss and Laplace, at most 64 coordinates) ----
+    def _unscaled_gradient(self, G):
+        """a gradient in the model's coordinates t / widths in the caller's: the chain rule divides by widths"""
+        return G if self.widths is None else G / self.widths
+
+    def predict_gradient(self, T):
+        """(m, d): the gradient of decision_function in the rows of T, sum_r alpha_r dk(x_r, t) / dt -- a force, where the fit is an
+        energy surface.  With widths set the result is in the caller's coordinates.  No kept model needed."""
+        if self.dtype == np.float32:
+            raise RuntimeError("predict_gradient: a double fit is needed")
+        T = np.ascontiguousarray(self._scaled(np.asarray(T, dtype=np.float64), "predict_gradient"))
+        if T.ndim != 2 or T.shape[1] != self.d:
+            raise ValueError("predict_gradient: an m x d array of test points is expected")
+        G = np.zeros((T.shape[0], self.d))
+        if self.L.SPX_kernel_predict_gradient_double(self.K, T.shape[0], T.ctypes.data, G.ctypes.data):
+            raise RuntimeError("SPX_kernel_predict_gradient_double failed (a double Gauss or Laplace fit in at most 64 coordinates is needed)")
+        return self._unscaled_gradient(G)
+
+    def predict_variance_gradient(self, T, exact=False, rtol=1e-8, maxit=100, restart=30, info=False, inner=None, inner_rtol=None):
+        """(var, grad[, info]): predict_variance(T, ...) -- the same values, bit for bit -- and its gradient in the rows of T, (m, d):
+        -2 sum_r V_r dk(x_r, t) / dt with V = H^-1 k(X, t) (exact=True: the exact solve).  This is the derivative of the returned
+        variance exactly when the kept matrix is symmetric; otherwise it is -2 D^T H^-1 k.  With widths set the gradient is in
+        the caller's coordinates.  The other arguments: see predict_variance."""
+        if self.dtype == np.float32:
+            raise RuntimeError("predict_variance_gradient: a double fit is needed")
+        T = np.ascontiguousarray(self._scaled(np.asarray(T, dtype=np.float64), "predict_variance_gradient"))
+        if T.ndim != 2 or T.shape[1] != self.d:
+            raise ValueError("predict_variance_gradient: an m x d array of test points is expected")
+        m = T.shape[0]
+        var, G = np.zeros(m), np.zeros((m, self.d))
+        if not exact:
+            if self.L.SPX_kernel_predict_variance_gradient_double(self.K, m, T.ctypes.data, var.ctypes.data, G.ctypes.data):
+                raise RuntimeError("SPX_kernel_predict_variance_gradient_double failed (a kept model of a Gauss or Laplace fit in at most "
+                                   "64 coordinates is needed)")
+            return var, self._unscaled_gradient(G)
+        buf = np.zeros(8 + 2 * m)
+        with self._inner(inner, inner_rtol):
+            if self.L.SPX_kernel_predict_variance_gradient_exact_double(self.K, m, T.ctypes.data, var.ctypes.data, G.ctypes.data, float(rtol),
+                                                                        int(maxit), int(restart), buf.ctypes.data):
+                raise RuntimeError("SPX_kernel_predict_variance_gradient_exact_double failed (a kept model of a Gauss or Laplace fit in at "
+                                   "most 64 coordinates and valid rtol / maxit / restart are needed)")
+            G = self._unscaled_gradient(G)
+            return (var, G, self._krylov_stats(self._krylov_info(buf))) if info else (var, G)
 
     # ---- the precision of the product inside the cycles of refine / solve / predict_variance(exact=True) ----
     def set_krylov_inner(self, inner="f64", inner_rtol=None):
