@@ -107,7 +107,7 @@ int hssk_side_join(hssk_ctx* ctx);
 int hssk_stream_wait(hssk_ctx* waiter, hssk_ctx* on);
 /* Device-clock stopwatches on the compute stream: hssk_watch_start / _stop bracket the launches in between with HIP events
  * (any number of start / stop pairs per stopwatch); hssk_watch_read_ms synchronises, returns the summed duration of
- * stopwatch `id` (0 .. 7) in ms, writes the number of pairs to *pairs (may be NULL) and clears it.  This is how bench.py
+ * stopwatch `id` (0 .. 10) in ms, writes the number of pairs to *pairs (may be NULL) and clears it.  This is how bench.py
  * times one kind of kernel inside a timed region without a host synchronisation per launch. */
 int hssk_watch_start(hssk_ctx* ctx, int id);
 int hssk_watch_stop(hssk_ctx* ctx, int id);
@@ -894,6 +894,26 @@ int hssk_logabsdet_vbatched(hssk_ctx* ctx, const hssk_logdet_desc* descs, int co
 int hssk_kernel_matmul(hssk_ctx* ctx, const hssk_kernel_spec* spec, int deriv, const double* B, long long ldb, int nc, double* out,
                        long long ldo, int splits);
 int hssk_kernel_matmul_splits(long long n);   /* what splits = 0 chooses: a function of n alone */
+/* The block of hssk_kernel_cross, out(r, c) = k(x_r, t_c), on a grid of (tiles of 64 test points) x (ranges of whole 64-point
+ * tiles of the training points): the same pair arithmetic, the same types (0 .. 4) and any d >= 1, and -- an entry depends on its
+ * pair alone -- bit for bit the same block for every split count.  It touches the same memory: rows n .. ldo - 1 and the columns
+ * from m on are never written.  splits = 0 takes hssk_kernel_cross_splits(n, m), a positive value forces the count (at most one
+ * split per 64 training points).  m = 0 or n = 0: nothing to do. */
+int hssk_kernel_cross_split(hssk_ctx* ctx, const hssk_kernel_spec* spec, const double* T, int m, double* out, long long ldo, int splits);
+int hssk_kernel_cross_splits(long long n, int m);   /* what splits = 0 chooses: a function of (n, m) alone */
+/* out(a, c) = sum_r k(t_a, x_r) B(r, c), a < m, c < nc, 1 <= nc <= 64: the product of the rectangular cross-kernel block between
+ * m test points (T: device, d x m) and the spec's n points with a block of vectors, the block never stored.  B: device, n x nc
+ * column-major, ldb >= n; out: device, m x nc, ldo >= m, may not alias B; the rows m .. ldo - 1 and the columns from nc on are not
+ * touched.  There is no lambda term: spec->lambda is ignored.  Gauss, Laplace and Matern, any d >= 1 (beyond 64 coordinates the
+ * points pass through the LDS 32 coordinates at a time); ANOVA returns HSSK_UNSUPPORTED (2) and writes nothing.  The grid is
+ * (tiles of 64 test points) x (splits of the training points) on the stages of hssk_kernel_matmul: splits = 0 takes
+ * hssk_kernel_cross_matmul_splits(n, m), a positive value forces the count (at most one split per 16 training points).  Split
+ * partials go to slabs the context keeps and are added in split order (hssk_sum_slabs): no atomics, bitwise repeatable.  nc
+ * outside 1 .. 64, ldb < n, ldo < m and a null pointer where one is read are refused (1) with nothing written.  m = 0: nothing to
+ * do; n = 0 and m > 0: the block is zeroed. */
+int hssk_kernel_cross_matmul(hssk_ctx* ctx, const hssk_kernel_spec* spec, const double* T, int m, const double* B, long long ldb, int nc,
+                             double* out, long long ldo, int splits);
+int hssk_kernel_cross_matmul_splits(long long n, int m);   /* what splits = 0 chooses: a function of (n, m) alone */
 /* out_j(i, c) = sum_r k(x_i, x_r) D_j(x_i, x_r) B(r, c) for the nj coordinates j = j0 .. j0 + nj - 1 in ONE pass over the pairs
  * (one distance and one exponential per pair serve all of them): D_j = (x_j - y_j)^2 / h^2 (Gauss), |x_j - y_j| / h (Laplace),
  * the derivative of k(x / l, y / l) in ln l_j at l = 1, so that sum_j k D_j = h dk/dh.  Block j is n x nc,

@@ -153,6 +153,16 @@ int SPX_kernel_predict_variance_gradient_double(STRUMPACKKernel K, int m, const 
  * refusals as there (SPX_kernel_set_krylov_inner is respected; the gradient sum itself is always FP64) */
 int SPX_kernel_predict_variance_gradient_exact_double(STRUMPACKKernel K, int m, const double* test, double* var, double* grad, double rtol,
                                                       int maxit, int restart, double* info);
+/* ---- the joint predictive covariance of the m test points: cov(a, b) = k(t_a, t_b) - (Q(a, b) + Q(b, a)) / 2,
+ * Q = k(T, X) H^-1 k(X, T), column-major with ldc >= m; exactly symmetric, not clamped.  Its diagonal agrees with
+ * SPX_kernel_predict_variance_double within rounding, not bit for bit (the sums run in another order).  Gauss and Laplace
+ * fits, any d; non-zero, outputs untouched, without a kept model, for an ANOVA fit or a float handle. */
+int SPX_kernel_predict_covariance_double(STRUMPACKKernel K, int m, const double* test, double* cov, int ldc);
+/* the same with the exact solve; rtol, maxit, restart and info as for SPX_kernel_predict_variance_exact_double */
+int SPX_kernel_predict_covariance_exact_double(STRUMPACKKernel K, int m, const double* test, double* cov, int ldc, double rtol, int maxit,
+                                               int restart, double* info);
+/* device-clock milliseconds of the last covariance call: ms3[0] cross-kernel blocks, [1] solves, [2] products */
+int SPX_kernel_covariance_ms(STRUMPACKKernel K, double* ms3);
 /* binary_tree_clustering on its own (clustering/Clustering.hpp:143-168): algo 0 natural, 1 2means, 2 kdtree,
  * 3 pca, 4 cobble; data (d x n) is reordered in place, perm is 1-based; returns the number of leaves and writes
  * at most cap leaf sizes */

@@ -120,6 +120,58 @@ std::vector<double> Kernel<double>::variance_chunks(const Model& M, const DenseM
   return var;
 }
 
+DenseMatrix<double> Kernel<double>::predict_covariance(const DenseMatrix<double>& test) const {
+  const Model& M = model("predict_covariance");
+  require_exact_products(*this, "predict_covariance");
+  if (test.rows() != d()) throw std::invalid_argument("predict_covariance: test points have the wrong dimension");
+  return covariance_chunks(M, test, nullptr, 0., 0, 0, nullptr);
+}
+
+// Stopwatches 8 / 9 / 10: cross blocks, solves, products (1 .. 3 are the variance loop's, 4 .. 7 those of the Krylov code this may
+// run around).
+DenseMatrix<double> Kernel<double>::covariance_chunks(const Model& M, const DenseMatrix<double>& test, KrylovWork* ws, double rtol, int maxit,
+                                                      int restart, KrylovInfo* info) const {
+  const int m = int(test.cols()), dim = int(d()), CH = 64;
+  const long long nn = (long long)n();
+  cov_ms_[0] = cov_ms_[1] = cov_ms_[2] = 0.;
+  DenseMatrix<double> C(m, m);
+  if (m == 0) return C;
+  hssk_ctx* ctx = M.ctx();
+  for (int w = 8; w <= 10; w++) hssk_watch_read_ms(ctx, w, nullptr);   // (what a call that threw left recorded is dropped)
+  PoolBuf bT(ctx, sizeof(double) * dim * m), bK(ctx, sizeof(double) * nn * CH), bQ(ctx, sizeof(double) * m * m), bC(ctx, sizeof(double) * m * m);
+  double *dT = (double*)bT.p, *dK = (double*)bK.p, *dQ = (double*)bQ.p, *dC = (double*)bC.p;
+  ckk(hssk_memcpy2d_h2d(ctx, dT, sizeof(double) * dim, test.data(), sizeof(double) * test.ld(), sizeof(double) * dim, m));
+  const hssk_kernel_spec spec = kept_spec(*this, M.dX, 0.);
+  // k(T, T) by the same pair function: the test points as the point set
+  const hssk_kernel_spec self{dT, (long long)m, dim, device_type(), degree(), width(), 0.};
+  watched(ctx, 8, [&] { ckk(hssk_kernel_cross_split(ctx, &self, dT, m, dC, m, 0)); });
+  for (int c0 = 0; c0 < m; c0 += CH) {
+    const int mc = std::min(CH, m - c0);
+    const double* dTc = dT + (size_t)c0 * dim;
+    watched(ctx, 8, [&] { ckk(hssk_kernel_cross_split(ctx, &spec, dTc, mc, dK, nn, 0)); });
+    if (ws) ckk(hssk_memcpy_d2d(ctx, ws->B, dK, (long long)sizeof(double) * nn * mc));   // (the right-hand sides of the exact solve)
+    watched(ctx, 9, [&] { M.H.solve_device(mc, dK, nn); });
+    if (ws) {   // from H^-1 k on: the exact solve of the chunk's columns
+      info->solves++;
+      krylov_block(M, *ws, mc, dK, ws->B, rtol, maxit, restart, *info);
+    }
+    // Q(:, chunk) = k(T, X) V: every test point against the chunk's solved columns
+    watched(ctx, 10, [&] { ckk(hssk_kernel_cross_matmul(ctx, &spec, dT, m, dK, nn, mc, dQ + (size_t)c0 * m, m, 0)); });
+  }
+  DenseMatrix<double> Q(m, m);
+  ckk(hssk_memcpy_d2h(ctx, Q.data(), dQ, (long long)sizeof(double) * m * m));
+  ckk(hssk_memcpy_d2h(ctx, C.data(), dC, (long long)sizeof(double) * m * m));
+  for (int w = 0; w < 3; w++) cov_ms_[w] = hssk_watch_read_ms(ctx, w + 8, nullptr);
+  // one value per pair {a, b}, stored twice: exactly symmetric whatever H^-1 is
+  for (int b = 0; b < m; b++)
+    for (int a = b; a < m; a++) {
+      const double v = C(a, b) - 0.5 * (Q(a, b) + Q(b, a));
+      C(a, b) = v;
+      C(b, a) = v;
+    }
+  return C;
+}
+
 DenseMatrix<double> Kernel<double>::fit_HSS(std::vector<double>& labels, const HSS::HSSOptions<double>& opts) {
   if (labels.size() != n()) throw std::invalid_argument("fit_HSS: one label per training point expected");
   model_.reset();   // (the model of an earlier fit goes before the new compression asks for memory)

@@ -186,6 +186,23 @@ template <> class Kernel<double> {
                                                         int maxit = 100, int restart = 30) const;
   // device-clock milliseconds of the last of these three calls: exact products, ULV solves, Krylov kernels (profiling)
   const double* krylov_ms() const { return kry_ms_; }
+  // ---- extension: the JOINT predictive covariance of the test points from the kept model (Gauss and Laplace).
+  //   C = k(T, T) - (Q + Q^T) / 2,   Q = k(T, X) V,   V = H^-1 k(X, T),   m x m for test = d x m, any d.
+  // Per chunk of 64 test points on the model's stream, no host wait in between: the cross block on a grid over both point sets
+  // (hssk_kernel_cross_split), the ULV solve in place, and the product of the rectangular cross block of ALL test points with
+  // the solved columns on the FP64 matrix cores (hssk_kernel_cross_matmul) into the chunk's columns of Q.  The kept compressed
+  // matrix is not exactly symmetric, so Q is symmetrised, once, at the end: C(a, b) == C(b, a) bit for bit.  The sums run in
+  // another order than those of predict_variance: the diagonal agrees with it within the two calls' rounding bounds, NOT bit
+  // for bit.  Not clamped (a loosely compressed fit can give an indefinite C).  n x 64 + 2 m^2 doubles come from the device
+  // pool beside the test points; a pool that refuses them raises the pool's own error.  Throws without a kept model, for an
+  // ANOVA kernel and for test points of the wrong dimension.
+  DenseM_t predict_covariance(const DenseM_t& test) const;
+  // the same with the exact solve in place of the compressed one (as predict_variance_exact: GMRES from H^-1 k on, krylov_inner
+  // respected, not converging reported in info, not thrown)
+  DenseM_t predict_covariance_exact(const DenseM_t& test, KrylovInfo* info = nullptr, scalar_t rtol = 1e-8, int maxit = 100,
+                                    int restart = 30) const;
+  // device-clock milliseconds of the last covariance call: cross-kernel blocks, ULV solves, products (profiling)
+  const double* covariance_ms() const { return cov_ms_; }
   // ---- extension: mixed precision for these three calls.  Handle state, set like keep_model; FP64 is the default
   // and leaves every call what it was, bit for bit.  With FP32 the product inside a cycle is hssk_kernel_matmul_f32 (FP32 per
   // pair on the matrix cores, from float points prepared once per call); the product at a cycle's start -- the true residual,
@@ -231,6 +248,7 @@ template <> class Kernel<double> {
   bool keep_model_ = false;
   mutable double var_ms_[3] = {0., 0., 0.};
   mutable double grad_ms_[3] = {0., 0., 0.};
+  mutable double cov_ms_[3] = {0., 0., 0.};
   mutable double kry_ms_[4] = {0., 0., 0., 0.};
   mutable double kry_stats_[6] = {0., 0., 0., 0., 0., 0.};
   KrylovInner inner_ = KrylovInner::FP64;
@@ -253,6 +271,8 @@ template <> class Kernel<double> {
   // points (resized to d x m), from the chunk's solved columns
   std::vector<scalar_t> variance_chunks(const Model& M, const DenseM_t& test, KrylovWork* ws, scalar_t rtol, int maxit, int restart,
                                         KrylovInfo* info, DenseM_t* grad = nullptr) const;
+  // the chunk loop of the covariance calls; ws == nullptr: the compressed solve
+  DenseM_t covariance_chunks(const Model& M, const DenseM_t& test, KrylovWork* ws, scalar_t rtol, int maxit, int restart, KrylovInfo* info) const;
   // what the gradients in the test points take: throws for a user-defined or ANOVA kernel and for d > 64
   void require_point_gradient(const char* what) const;
 };

@@ -360,6 +360,27 @@ int SPX_kernel_predict_variance_gradient_exact_double(STRUMPACKKernel K, int m, 
     return 0;
   });
 }
+// ---- the joint predictive covariance ----
+int SPX_kernel_covariance_ms(STRUMPACKKernel K, double out[3]) { return array_out(K, out, &KernelD::covariance_ms, 3, true); }
+int SPX_kernel_predict_covariance_double(STRUMPACKKernel K, int m, const double* test, double* cov, int ldc) {
+  return with_model(K, [&](KernelD& k) {
+    if (m < 0 || (m > 0 && (!test || !cov || ldc < m))) return 1;
+    const DenseMatrix<double> c = k.predict_covariance(DenseMatrix<double>(k.d(), m, test, k.d()));
+    for (int b = 0; b < m; b++) std::copy(c.ptr(0, b), c.ptr(0, b) + m, cov + (std::size_t)b * ldc);
+    return 0;
+  });
+}
+int SPX_kernel_predict_covariance_exact_double(STRUMPACKKernel K, int m, const double* test, double* cov, int ldc, double rtol, int maxit,
+                                               int restart, double* info) {
+  return with_model(K, [&](KernelD& k) {
+    if (m < 0 || (m > 0 && (!test || !cov || ldc < m))) return 1;
+    kernel::KrylovInfo I;
+    const DenseMatrix<double> c = k.predict_covariance_exact(DenseMatrix<double>(k.d(), m, test, k.d()), &I, rtol, maxit, restart);
+    for (int b = 0; b < m; b++) std::copy(c.ptr(0, b), c.ptr(0, b) + m, cov + (std::size_t)b * ldc);
+    krylov_info_out(I, info);
+    return 0;
+  });
+}
 int SPX_kernel_set_krylov_inner(STRUMPACKKernel K, int precision, double inner_rtol) {
   return guarded([&] {
     auto k = builtin_of(K);

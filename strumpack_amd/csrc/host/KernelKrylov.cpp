@@ -225,6 +225,19 @@ std::vector<double> Kernel<double>::predict_variance_exact(const DenseMatrix<dou
   return var;
 }
 
+DenseMatrix<double> Kernel<double>::predict_covariance_exact(const DenseMatrix<double>& test, KrylovInfo* info, double rtol, int maxit, int restart) const {
+  const Model& M = krylov_model("predict_covariance_exact", rtol, maxit, restart);
+  if (test.rows() != d()) throw std::invalid_argument("predict_covariance_exact: test points have the wrong dimension");
+  KrylovInfo local;
+  if (test.cols() == 0) { if (info) *info = local; return DenseMatrix<double>(0, 0); }
+  KrylovWork ws(M.ctx(), (long long)n(), 64, maxit, restart, false, krylov_prep_bytes());
+  krylov_prepare(M, ws);
+  DenseMatrix<double> C = covariance_chunks(M, test, &ws, rtol, maxit, restart, &local);
+  krylov_finish(M, local);
+  if (info) *info = local;
+  return C;
+}
+
 std::vector<double> Kernel<double>::predict_variance_gradient_exact(const DenseMatrix<double>& test, DenseMatrix<double>& grad, KrylovInfo* info,
                                                                     double rtol, int maxit, int restart) const {
   const Model& M = krylov_model("predict_variance_gradient_exact", rtol, maxit, restart);

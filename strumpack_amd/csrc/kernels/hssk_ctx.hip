@@ -276,7 +276,7 @@ void hssk_ctx_destroy(hssk_ctx* c) {
       // a context abandoned in the middle of something (an exception between a stopwatch's start and stop, or inside a
       // side-stream section) goes back to the pool in its neutral state
       if (c->on_side) { c->stream = c->main_saved; c->on_side = false; }
-      for (int i = 0; i < 8; i++) {
+      for (int i = 0; i < hssk_ctx::WATCHES; i++) {
         for (auto& p : c->watch[i]) { c->watch_free.push_back(p.first); c->watch_free.push_back(p.second); }
         c->watch[i].clear();
         c->watch_open[i] = false;
@@ -368,7 +368,7 @@ static hssk_rt::event_t watch_event(hssk_ctx* c) {
 }
 int hssk_watch_start(hssk_ctx* c, int id) {
   HSSK_API_BEGIN
-  if (id < 0 || id >= 8) throw std::invalid_argument("hssk_watch_start: id out of range");
+  if (id < 0 || id >= hssk_ctx::WATCHES) throw std::invalid_argument("hssk_watch_start: id out of range");
   if (c->watch_open[id]) {
     // left open by a caller that threw between start and stop: the interval is dropped, the stopwatch starts over
     auto p = c->watch[id].back();
@@ -385,14 +385,14 @@ int hssk_watch_start(hssk_ctx* c, int id) {
 }
 int hssk_watch_stop(hssk_ctx* c, int id) {
   HSSK_API_BEGIN
-  if (id < 0 || id >= 8 || !c->watch_open[id]) throw std::logic_error("hssk_watch_stop: stopwatch is not running");
+  if (id < 0 || id >= hssk_ctx::WATCHES || !c->watch_open[id]) throw std::logic_error("hssk_watch_stop: stopwatch is not running");
   hssk_rt::event_record(c->watch[id].back().second, c->stream);
   c->watch_open[id] = false;
   HSSK_API_END
 }
 double hssk_watch_read_ms(hssk_ctx* c, int id, int* pairs) {
   if (pairs) *pairs = 0;
-  if (!c || id < 0 || id >= 8) return 0.;
+  if (!c || id < 0 || id >= hssk_ctx::WATCHES) return 0.;
   try {
     if (c->watch_open[id]) { hssk_rt::event_record(c->watch[id].back().second, c->stream); c->watch_open[id] = false; }
     hssk_rt::sync(c->stream);

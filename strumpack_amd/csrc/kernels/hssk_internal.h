@@ -71,9 +71,10 @@ struct hssk_ctx {
   int* d_sweep_flags = nullptr;
   int* h_sweep_err = nullptr;
   // stopwatches (hssk_watch_*): recorded event pairs per id, recycled through a free list
-  std::vector<std::pair<hssk_rt::event_t, hssk_rt::event_t>> watch[8];
+  static constexpr int WATCHES = 11;
+  std::vector<std::pair<hssk_rt::event_t, hssk_rt::event_t>> watch[WATCHES];
   std::vector<hssk_rt::event_t> watch_free;
-  bool watch_open[8] = {false, false, false, false, false, false, false, false};
+  bool watch_open[WATCHES] = {};
   size_t sweep_cap = size_t(1) << 20;
   size_t scratch_bytes = 0;
   long long knn_filtered = 0;   // calls of hssk_knn the filtered search answered (hssk_knn_filtered_count)

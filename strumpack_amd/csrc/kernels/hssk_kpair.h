@@ -8,6 +8,8 @@
 //   PR_CROSS  out(r, c) = k             (no sum)
 // The value itself -- the order of the coordinates, the exponentials, Newton's identities of the ANOVA kernel -- is one piece of
 // code for the three, and the sums of PR_SUM and PR_COLS take the pairs of a test point in the same order.
+// SPLIT (PR_CROSS only, hssk_kernel_cross_split): the grid has a second dimension over ranges of whole 64-point tiles of the
+// training points (pr_split_per); an entry depends on its pair alone, so the block is bit for bit that of the one-dimensional grid.
 #pragma once
 #include "hssk_device.h"
 #include "hssk_internal.h"
@@ -23,10 +25,16 @@ constexpr int PR_SUM = 0, PR_COLS = 1, PR_CROSS = 2;
 constexpr size_t PR_LDS_POINT = sizeof(double) * (2 * PR_T * (PR_DMAX + 1) + PR_T);
 constexpr size_t PR_LDS_WIDE = sizeof(double) * (PR_T * (PR_DC + 1) + 32 * PR_DC + 32);
 
+// training points per split of a SPLIT grid of s ranges: whole tiles of PR_T (a multiple of every RT of the wide kernel)
+__host__ __device__ inline long long pr_split_per(long long n, long long s) {
+  const long long tiles = (n + PR_T - 1) / PR_T;
+  return ((tiles + s - 1) / s) * PR_T;
+}
+
 // prediction[c] = sum_r w[r] k(x_r, t_c)   (no lambda: train and test points are different sets)
 // MAT: the Matern kernels (types 3 and 4) -- the Gauss distance loop with the finish of hssk_matern.h; an instantiation of its
 // own, so that the code of the other three kernels is what it was
-template <int MODE, bool MAT = false>
+template <int MODE, bool MAT = false, bool SPLIT = false>
 __global__ __launch_bounds__(PR_T) void kernel_predict_kernel(hssk_kernel_spec ks, const double* __restrict__ w, size_t ldw,
                                                               const double* __restrict__ T, int m,
                                                               double* __restrict__ pred, size_t ldo) {
@@ -37,7 +45,9 @@ __global__ __launch_bounds__(PR_T) void kernel_predict_kernel(hssk_kernel_spec k
   const bool live = c < m;
   for (int j = 0; j < d; j++) xt[tid * (PR_DMAX + 1) + j] = live ? T[(size_t)c * d + j] : 0.;
   double sum = 0.;
-  for (long long r0 = 0; r0 < ks.n; r0 += PR_T) {
+  const long long rb = SPLIT ? (long long)blockIdx.y * pr_split_per(ks.n, gridDim.y) : 0;
+  const long long re = SPLIT ? min(ks.n, rb + pr_split_per(ks.n, gridDim.y)) : ks.n;
+  for (long long r0 = rb; r0 < re; r0 += PR_T) {
     __syncthreads();
     for (int e = tid; e < PR_T * d; e += PR_T) {
       const int pt = e / d, j = e % d;
@@ -45,7 +55,7 @@ __global__ __launch_bounds__(PR_T) void kernel_predict_kernel(hssk_kernel_spec k
     }
     if (MODE == PR_SUM) wr[tid] = r0 + tid < ks.n ? w[r0 + tid] : 0.;
     __syncthreads();
-    const int rend = (int)min((long long)PR_T, ks.n - r0);
+    const int rend = (int)min((long long)PR_T, re - r0);
     for (int r = 0; r < rend; r++) {
       double v;
       if (MAT) {
@@ -109,7 +119,7 @@ __device__ inline void anova_newton<0>(const double (&)[8], double (&K)[9], int,
 // hold (32 distances, 8 x 8 power sums; the Matern kernels, TYPE 3 and 4, carry the Gauss distance).  Per pair the coordinates are met in order and the pairs of a test point in training
 // order, as in kernel_predict_kernel: the same arithmetic, the same error bound.  The test points' pass is staged again for
 // every training tile (one staged value per RT differences).
-template <int TYPE, int RT, int MODE>
+template <int TYPE, int RT, int MODE, bool SPLIT = false>
 __global__ __launch_bounds__(PR_T) void kernel_predict_wide_kernel(hssk_kernel_spec ks, const double* __restrict__ w, size_t ldw,
                                                                    const double* __restrict__ T, int m, double* __restrict__ pred,
                                                                    size_t ldo) {
@@ -120,7 +130,9 @@ __global__ __launch_bounds__(PR_T) void kernel_predict_wide_kernel(hssk_kernel_s
   const int tid = threadIdx.x, cb = blockIdx.x * PR_T, c = cb + tid, d = ks.d, P = ks.p;
   const double h2 = 2. * ks.h * ks.h;
   double sum = 0.;
-  for (long long r0 = 0; r0 < ks.n; r0 += RT) {
+  const long long rb = SPLIT ? (long long)blockIdx.y * pr_split_per(ks.n, gridDim.y) : 0;
+  const long long re = SPLIT ? min(ks.n, rb + pr_split_per(ks.n, gridDim.y)) : ks.n;
+  for (long long r0 = rb; r0 < re; r0 += RT) {
     double acc[RT][NS];
 #pragma unroll
     for (int r = 0; r < RT; r++)
@@ -157,7 +169,7 @@ __global__ __launch_bounds__(PR_T) void kernel_predict_wide_kernel(hssk_kernel_s
         }
       }
     }
-    const int rend = (int)min((long long)RT, ks.n - r0);
+    const int rend = (int)min((long long)RT, re - r0);
 #pragma unroll
     for (int r = 0; r < RT; r++)
       if (r < rend) {

@@ -177,6 +177,7 @@ HSSK_SYMBOLS = [
     "hssk_kernel_matmul_coord", "hssk_kernel_matmul_coord_max", "hssk_kernel_matmul_coord_group",
     "hssk_krylov_start", "hssk_krylov_orth", "hssk_krylov_combine",
     "hssk_kernel_matmul_f32", "hssk_kernel_matmul_f32_prep", "hssk_kernel_matmul_f32_prep_bytes", "hssk_kernel_matmul_f32_splits",
+    "hssk_kernel_cross_split", "hssk_kernel_cross_splits", "hssk_kernel_cross_matmul", "hssk_kernel_cross_matmul_splits",
 ]
 
 
@@ -309,6 +310,12 @@ class Hssk:
         L.hssk_kernel_matmul.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong,
                                          C.c_int]
         L.hssk_kernel_matmul_splits.argtypes = [C.c_longlong]
+        # the cross block on the split grid: T, m, out, ldo, splits; its product with a block: T, m, B, ldb, nc, out, ldo, splits
+        L.hssk_kernel_cross_split.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_int]
+        L.hssk_kernel_cross_splits.argtypes = [C.c_longlong, C.c_int]
+        L.hssk_kernel_cross_matmul.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
+                                               C.c_longlong, C.c_int]
+        L.hssk_kernel_cross_matmul_splits.argtypes = [C.c_longlong, C.c_int]
         # per-coordinate derivatives: j0, nj in front of B; the stride between the nj output blocks behind ldo
         L.hssk_kernel_matmul_coord.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
                                                C.c_longlong, C.c_longlong, C.c_int]

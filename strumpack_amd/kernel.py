@@ -18,6 +18,7 @@ KERNEL_SYMBOLS = [
     "SPX_kernel_krylov_ms", "SPX_kernel_set_krylov_inner", "SPX_kernel_krylov_inner", "SPX_kernel_krylov_stats",
     "SPX_kernel_predict_gradient_double", "SPX_kernel_predict_variance_gradient_double",
     "SPX_kernel_predict_variance_gradient_exact_double",
+    "SPX_kernel_predict_covariance_double", "SPX_kernel_predict_covariance_exact_double", "SPX_kernel_covariance_ms",
 ]
 KRYLOV_INNER = {"f64": 0, "f32": 1}
 KERNEL_TYPES = {"Gauss": 0, "rbf": 0, "Laplace": 1, "ANOVA": 2}
@@ -66,6 +67,9 @@ def load(path):
     L.SPX_kernel_predict_gradient_double.argtypes = [vp, C.c_int, vp, vp]
     L.SPX_kernel_predict_variance_gradient_double.argtypes = [vp, C.c_int, vp, vp, vp]
     L.SPX_kernel_predict_variance_gradient_exact_double.argtypes = [vp, C.c_int, vp, vp, vp, C.c_double, C.c_int, C.c_int, vp]
+    L.SPX_kernel_predict_covariance_double.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+    L.SPX_kernel_predict_covariance_exact_double.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp]
+    L.SPX_kernel_covariance_ms.argtypes = [vp, vp]
     L.SPX_kernel_krylov_ms.argtypes = [vp, vp]
     L.SPX_kernel_set_krylov_inner.argtypes = [vp, C.c_int, C.c_double]
     L.SPX_kernel_krylov_inner.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
@@ -201,6 +205,54 @@ class KernelRegression:
                                    "most 64 coordinates and valid rtol / maxit / restart are needed)")
             G = self._unscaled_gradient(G)
             return (var, G, self._krylov_stats(self._krylov_info(buf))) if info else (var, G)
+
+    # ---- the joint predictive covariance and draws from it (double fits, Gauss and Laplace) ----
+    def predict_covariance(self, T, exact=False, rtol=1e-8, maxit=100, restart=30, info=False, inner=None, inner_rtol=None):
+        """(m, m): the joint covariance of the latent function at the rows of T, k(T, T) - (Q + Q^T) / 2 with
+        Q = k(T, X) H^-1 k(X, T); exactly symmetric, not clamped (a loosely compressed fit can give an indefinite matrix).  Its
+        diagonal agrees with predict_variance(T) within rounding, not bit for bit: the sums run in another order.  With widths set
+        the rows of T are scaled like everywhere else; the covariance needs no scaling back.  The other arguments: see
+        predict_variance."""
+        if self.dtype == np.float32:
+            raise RuntimeError("predict_covariance: a double fit is needed")
+        T = np.ascontiguousarray(self._scaled(np.asarray(T, dtype=np.float64), "predict_covariance"))
+        if T.ndim != 2 or T.shape[1] != self.d:
+            raise ValueError("predict_covariance: an m x d array of test points is expected")
+        m = T.shape[0]
+        cov = np.zeros((m, m), order="F")
+        if not exact:
+            if self.L.SPX_kernel_predict_covariance_double(self.K, m, T.ctypes.data, cov.ctypes.data, m):
+                raise RuntimeError("SPX_kernel_predict_covariance_double failed (a kept model of a Gauss or Laplace fit is needed)")
+            return cov
+        buf = np.zeros(8 + 2 * m)
+        with self._inner(inner, inner_rtol):
+            if self.L.SPX_kernel_predict_covariance_exact_double(self.K, m, T.ctypes.data, cov.ctypes.data, m, float(rtol), int(maxit),
+                                                                 int(restart), buf.ctypes.data):
+                raise RuntimeError("SPX_kernel_predict_covariance_exact_double failed (a kept model of a Gauss or Laplace fit and valid "
+                                   "rtol / maxit / restart are needed; inner=\"f32\": at most 64 coordinates)")
+            return (cov, self._krylov_stats(self._krylov_info(buf))) if info else cov
+
+    def covariance_ms(self):
+        out = np.zeros(3)
+        if self.L.SPX_kernel_covariance_ms(self.K, out.ctypes.data):
+            raise RuntimeError("no kept double-precision Gauss or Laplace model")
+        return dict(zip(["cross_ms", "solve_ms", "product_ms"], out.tolist()))
+
+    def sample_posterior(self, T, nsamples, seed=0, exact=False, jitter=0.0, **krylov):
+        """(nsamples, m): joint draws of the LATENT function at the rows of T, mean + Z L^T with mean = decision_function(T) (for a
+        classification fit: the latent value, not its sign), Z = Generator(Philox(seed)).standard_normal((nsamples, m)) and
+        L = cholesky(predict_covariance(T, exact, **krylov) + jitter I).  Raises ValueError where that matrix is not positive
+        definite (a covariance from a loosely compressed fit can be indefinite)."""
+        C_ = self.predict_covariance(T, exact=exact, **krylov)
+        m = C_.shape[0]
+        A = C_ + float(jitter) * np.eye(m)
+        try:
+            Lc = np.linalg.cholesky(A)
+        except np.linalg.LinAlgError:
+            raise ValueError("sample_posterior: covariance + jitter I is not positive definite (smallest eigenvalue %.3e); use "
+                             "exact=True or a larger jitter" % (np.linalg.eigvalsh(A).min() if m else 0.0)) from None
+        Z = np.random.Generator(np.random.Philox(int(seed))).standard_normal((int(nsamples), m))
+        return np.asarray(self.decision_function(T), dtype=np.float64).reshape(1, m) + Z @ Lc.T
 
     # ---- the precision of the product inside the cycles of refine / solve / predict_variance(exact=True) ----
     def set_krylov_inner(self, inner="f64", inner_rtol=None):
